@@ -10,7 +10,15 @@ full projection step (predictor, CG pressure solve to convergence,
 corrector). value = interior cells updated per second over all ranks, in
 MLUPS.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line
+(per-kernel timers and the roofline on them come from the timed steps
+themselves). --full adds every measurement that takes runs of its own after
+the timed region: the other CG variant, the fixed-iteration CG microbench,
+the stream copy / triad roof, the host-buffer plugin step and the CPU
+baseline; without it their keys are null. --dump-outputs DIR writes the
+fields the last timed step left (u, v, w, p; T for convection) as
+DIR/<name>.npy in float64 (dump_outputs).
 For N > 1 launch with torch.distributed.run (one rank per GPU): the grid is
 split into N Z-slabs (hip_proj_create_slab), halo planes and CG dot products
 move over RCCL (a communicator our library creates from a unique id that
@@ -63,6 +71,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own: "
+                         "the other CG variant, the fixed-iteration CG microbench, the stream "
+                         "roof, the host-buffer plugin step and the CPU baseline (each still "
+                         "has its own switch below)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the fields of the last timed step to DIR/<name>.npy (float64; "
+                         "a fixed seeded sample of each above 48 MB in all)")
     ap.add_argument("--size", type=int, default=0,
                     help="grid points per axis (default 512; convection: 1024 x 1024 x 512)")
     ap.add_argument("--case", choices=("cavity", "tg", "convection"), default="cavity",
@@ -126,6 +142,36 @@ def parse():
 def progress(msg):
     """A progress line on stderr (long runs: one every minute or so)."""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes written over all fields and ranks
+DUMP_SEED = 20240229   # seed of the sample's flat indices
+
+
+def dump_outputs(dirname, ctx, names, rank, world):
+    """--dump-outputs: what a caller of the timed path receives after the last
+    timed step, hip_proj_get_field of every field in `names` (name -> field
+    id), as DIR/<name>.npy in float64 (N > 1: each rank's owned planes as
+    DIR/<name>.rank<r>.npy). Fields of at most DUMP_BYTES in all are written
+    whole, in the context's (z, y, x) shape; larger ones as the same
+    DUMP_BYTES / 8 / fields / ranks flat C-order indices of every field, drawn
+    once from numpy's default_rng(DUMP_SEED), so two builds run with the same
+    arguments write the same points."""
+    import numpy as np
+
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    loc, _ = ctx.owned()
+    idx = None
+    for name, fid in names.items():
+        a = ctx.get_field(fid)[loc]
+        if a.nbytes * len(names) * world > DUMP_BYTES:
+            if idx is None:
+                k = DUMP_BYTES // (8 * len(names) * world)
+                idx = np.random.default_rng(DUMP_SEED).integers(0, a.size, k)
+            a = a.reshape(-1)[idx]
+        np.save(out / (f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
 
 
 def dist_env():
@@ -299,6 +345,10 @@ def main():
     # region (sampled launches, hip_proj_get_clock_sample), so the line
     # says which clock its box ran at
     clk_mhz, clk_wg = ctx.clock_sample()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, {"u": A.HIP_FIELD_U, "v": A.HIP_FIELD_V,
+                                              "w": A.HIP_FIELD_W, "p": A.HIP_FIELD_P},
+                     rank, world)
 
     n_int = (n - 2) ** 3
     n_loc = (n - 2) ** 2 * (ctx.nz_local - 2)  # interior cells of this rank's slab
@@ -374,10 +424,11 @@ def main():
         measured_gbps = round(tot * world / elapsed / 1e9, 1) if measured_from else None
 
     # measured HBM roof of this GPU (same library, 16-B lanes), after the
-    # timed region
+    # timed region (--full: a run of its own)
     import ctypes as C
     cg, tr = C.c_double(0.0), C.c_double(0.0)
-    if lib.cfd_hip_stream_bench(local, 1 << 27, 5, C.byref(cg), C.byref(tr)) != A.CFD_SUCCESS:
+    if args.full and lib.cfd_hip_stream_bench(local, 1 << 27, 5, C.byref(cg),
+                                              C.byref(tr)) != A.CFD_SUCCESS:
         cg.value = tr.value = 0.0
 
     ranks = None
@@ -402,7 +453,7 @@ def main():
     progress("timed region done")
     fixed200 = {}
     cos_rhs = None
-    if world == 1 and not tg and args.fixed_cg_iters > 0:
+    if args.full and world == 1 and not tg and args.fixed_cg_iters > 0:
         import numpy as np
         xs = np.asarray(g.x)
         cx = np.cos(np.pi * xs)
@@ -420,7 +471,7 @@ def main():
     # warmup + 1 is timed (its CG iterations are that step's count), next to
     # the main run's own wall time of that step
     other = None
-    if not args.no_compare_cg_variant:
+    if args.full and not args.no_compare_cg_variant:
         progress("cg_variant_compare")
         ctx.close()
         ctx = make_ctx(1 - args.cg_variant)
@@ -464,14 +515,14 @@ def main():
     # transfers and the resident dirty-faces mode, beside the HBM-resident
     # step on the same steps; never `value`
     plug = None
-    if world == 1 and not tg and not args.no_plugin_step:
+    if args.full and world == 1 and not tg and not args.no_plugin_step:
         progress("plugin_step")
         ctx.close()
         ctx = None
         plug = plugin_step(n, g, params, make_ctx, args.plugin_steps)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not tg:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not tg:
         progress("cpu_baseline")
         cpu = cpu_baseline(n, args, k_mean)
 
@@ -483,6 +534,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_step, 3),
             "higher_is_better": True,
             "scaling": "strong",
@@ -668,6 +720,10 @@ def run_convection(args, rank, world, local, comm, lib, torch, dist):
                 ("p", A.HIP_FIELD_P), ("T", A.HIP_FIELD_T))}
         np.savez(f"{args.dump}.rank{rank}.npz", k0=glob.start, k1=glob.stop,
                  iters=np.array(iters), **out)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, {"u": A.HIP_FIELD_U, "v": A.HIP_FIELD_V,
+                                              "w": A.HIP_FIELD_W, "p": A.HIP_FIELD_P,
+                                              "T": A.HIP_FIELD_T}, rank, world)
     roof = None
     rms, rn = kt["relax"]
     r2ms, r2n = kt["relax2"]

@@ -170,8 +170,8 @@ def cavity512_re1000(n=512, steps=25, state_dir="/tmp/cav512_state", threads=8):
     `state_dir` after every step and a rerun resumes.
     Writes cavity{n}_re1000_steps.json (per step: CG iterations, initial /
     final residual, L2 and max |.| of u, v, w, p) and, after the steps in
-    CAV512_SNAP_STEPS, cavity{n}_re1000_step{s}_planes.npz (plane_samples of
-    u, v, w, p at k in CAV512_PLANES)."""
+    CAV512_SNAP_STEPS, cavity{n}_re1000_step{s}_k{kz}_planes.npz (plane_samples
+    of u, v, w, p at each k in CAV512_PLANES, one file per plane)."""
     import json
     import time
 
@@ -203,13 +203,15 @@ def cavity512_re1000(n=512, steps=25, state_dir="/tmp/cav512_state", threads=8):
         rec["steps"].append(row)
         print(json.dumps(row), flush=True)
         if s in CAV512_SNAP_STEPS:
-            planes = {}
-            for k in ("u", "v", "w", "p"):
-                for kz in CAV512_PLANES:
-                    if kz < n:
+            # one file per sampled plane (each stays below 1 MiB)
+            for kz in CAV512_PLANES:
+                if kz < n:
+                    planes = {}
+                    for k in ("u", "v", "w", "p"):
                         for key, val in plane_samples(getattr(f, k)[kz]).items():
                             planes[f"{k}_k{kz}_{key}"] = val
-            np.savez_compressed(HERE / f"cavity{n}_re1000_step{s}_planes.npz", **planes)
+                    np.savez_compressed(HERE / f"cavity{n}_re1000_step{s}_k{kz}_planes.npz",
+                                        **planes)
         out_json.write_text(json.dumps(rec, indent=1) + "\n")
         if s < steps:
             for k in ("u", "v", "w", "p"):
@@ -279,7 +281,25 @@ def convection(name: str, threads: int = 8):
     (HERE / f"convection_{name}.json").write_text(json.dumps(rec, indent=1) + "\n")
 
 
+def reference_abi(include_dir: str):
+    """reference_abi_digests.json: kind and per-member digests of every
+    declaration in the reference headers tests/test_abi_reference_text.py
+    names, parsed by that test's own parser from a reference checkout's
+    lib/include/cfd. Digests only, no header text."""
+    import json
+
+    from tests import test_abi_reference_text as T
+
+    decls = T.reference_digests(Path(include_dir))
+    rec = {"headers": T.REF_HEADERS, "digest": "sha256(member)[:16], members in order",
+           "declarations": {n: {"kind": k, "members": m} for n, (k, m) in sorted(decls.items())}}
+    (HERE / "reference_abi_digests.json").write_text(json.dumps(rec, indent=1) + "\n")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["reference_abi"]:
+        reference_abi(sys.argv[2])
+        sys.exit(0)
     oracle.set_threads(1)
     if sys.argv[1:2] and sys.argv[1] in CONV_CASES:
         convection(sys.argv[1])

@@ -4,21 +4,26 @@ Every struct, enum and function-pointer typedef that cfd_abi.h restates must
 declare the same members (or enumerators, or parameter types) in the same
 order with the same types as the reference declaration it cites:
 navier_stokes_solver.h:54-277, poisson_solver.h:53-233, grid.h:18-40,
-cfd_status.h:13-24, boundary_conditions.h:19-57. The reference is read as
-data only (this build container has it; the GPU box does not, so the test
-skips there).
+cfd_status.h:13-24, boundary_conditions.h:19-57.
+
+The reference's side is a recorded result, tests/golden/reference_abi_digests.json:
+for every declaration of those five headers its kind and one sha256 digest
+per member, in order (`make_golden.py reference_abi <the reference's
+lib/include/cfd>` parses the headers with this file's parser and writes it).
+No header text is stored; our header is parsed here and digested the same
+way, so a member that differs in name, type or position differs in digest.
 """
+import hashlib
+import json
 import re
 from pathlib import Path
 
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-REF = Path("/root/reference/lib/include/cfd")
+DIGESTS = ROOT / "tests" / "golden" / "reference_abi_digests.json"
 REF_HEADERS = ["core/cfd_status.h", "core/grid.h", "boundary/boundary_conditions.h",
                "solvers/navier_stokes_solver.h", "solvers/poisson_solver.h"]
-
-pytestmark = pytest.mark.skipif(not REF.is_dir(), reason="reference headers not present")
 
 
 def _clean(text: str) -> str:
@@ -77,13 +82,34 @@ def parse(text: str):
     return decls
 
 
+def member_digest(member) -> str:
+    """One parsed member (a declaration string, or an enumerator's (name,
+    value)) as the first 16 hex digits of its sha256."""
+    if not isinstance(member, str):
+        member = f"{member[0]} = {member[1]}"
+    return hashlib.sha256(member.encode()).hexdigest()[:16]
+
+
+def digests(decls: dict) -> dict:
+    """parse()'s result with every member replaced by its digest."""
+    return {name: (kind, [member_digest(m) for m in body])
+            for name, (kind, body) in decls.items()}
+
+
+def reference_digests(include_dir: Path) -> dict:
+    """digests() of REF_HEADERS under a reference checkout's lib/include/cfd
+    (what make_golden.py records)."""
+    ref = {}
+    for h in REF_HEADERS:
+        ref.update(parse((Path(include_dir) / h).read_text()))
+    return digests(ref)
+
+
 @pytest.fixture(scope="module")
 def both():
     ours = parse((ROOT / "include" / "cfd_hip" / "cfd_abi.h").read_text())
-    ref = {}
-    for h in REF_HEADERS:
-        ref.update(parse((REF / h).read_text()))
-    return ours, ref
+    rec = json.loads(DIGESTS.read_text())["declarations"]
+    return ours, {name: (d["kind"], d["members"]) for name, d in rec.items()}
 
 
 # what cfd_abi.h must restate (the types that cross the plugin boundary)
@@ -107,8 +133,8 @@ def test_parser_sees_the_reference_declarations(both):
     _, ref = both
     missing = [n for n in REQUIRED if n not in ref]
     assert not missing, missing
-    assert ref["struct NSSolver"][1][0] == "const char* name"
-    assert ref["ns_solver_backend_t"][1][-1] == ("NS_SOLVER_BACKEND_CUDA", 3)
+    assert ref["struct NSSolver"][1][0] == member_digest("const char* name")
+    assert ref["ns_solver_backend_t"][1][-1] == member_digest(("NS_SOLVER_BACKEND_CUDA", 3))
 
 
 @pytest.mark.parametrize("name", REQUIRED)
@@ -118,13 +144,17 @@ def test_declaration_matches_reference_text(both, name):
     kind_o, body_o = ours[name]
     kind_r, body_r = ref[name]
     assert kind_o == kind_r, (name, kind_o, kind_r)
-    assert body_o == body_r, f"{name}:\n ours {body_o}\n ref  {body_r}"
+    dig_o = [member_digest(m) for m in body_o]
+    differ = [i for i, (a, b) in enumerate(zip(dig_o, body_r)) if a != b]
+    assert dig_o == body_r, (f"{name}: ours {body_o}\n has {len(body_o)} members, the reference "
+                             f"{len(body_r)}; members that differ: {differ}")
 
 
 def test_no_extra_members_anywhere(both):
     """Every declaration cfd_abi.h shares with the reference is identical, not
     only the required ones."""
     ours, ref = both
+    ours = digests(ours)
     shared = [n for n in ours if n in ref]
     assert len(shared) >= len(REQUIRED)
     bad = [n for n in shared if ours[n] != ref[n]]

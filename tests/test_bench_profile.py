@@ -87,6 +87,35 @@ def test_sweep_symbols_track_the_variant():
     assert dict((t, b) for t, _, b in bench.sweep_kernels(16, True, 15, 1, 64))["cc_spmv"] == 0.25
 
 
+def test_dump_outputs_sample_is_fixed(tmp_path):
+    """--dump-outputs: above DUMP_BYTES in all, every field is written as the
+    same seeded flat sample, the same points from run to run, within the
+    byte budget; smaller fields whole."""
+    import numpy as np
+
+    class Ctx:
+        def __init__(self, shape):
+            self.shape = shape
+
+        def owned(self):
+            return slice(0, self.shape[0]), slice(0, self.shape[0])
+
+        def get_field(self, fid):
+            return np.arange(np.prod(self.shape), dtype=np.float64).reshape(self.shape) + fid
+
+    small, big = Ctx((3, 5, 7)), Ctx((200, 200, 200))  # 840 B and 64 MB a field
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, big, {"u": 0, "v": 1}, 0, 1)
+    bench.dump_outputs(tmp_path / "s", small, {"u": 0, "v": 1}, 0, 1)
+    assert np.load(tmp_path / "s" / "v.npy").shape == (3, 5, 7)
+    u, v = np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "a" / "v.npy")
+    assert u.dtype == np.float64 and u.ndim == 1
+    assert 0 < u.nbytes + v.nbytes <= bench.DUMP_BYTES
+    np.testing.assert_array_equal(v, u + 1)  # the same points of every field
+    assert len(np.unique(u)) > 0.5 * u.size and u.min() >= 0 and u.max() < 200 ** 3
+    np.testing.assert_array_equal(u, np.load(tmp_path / "b" / "u.npy"))
+
+
 def test_cg_probe_rule():
     import argparse
     a = lambda probe, case="cavity": argparse.Namespace(cg_probe=probe, case=case)

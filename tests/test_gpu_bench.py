@@ -31,7 +31,7 @@ def _env():
 
 def test_bench_one_gpu_contract(hip_lib):
     r = subprocess.run([sys.executable, "bench.py", "--size", "66", "--steps", "2", "--warmup",
-                        "1", "--cpu-cg-iters", "2"], cwd=ROOT, env=_env(), capture_output=True,
+                        "1", "--cpu-cg-iters", "2", "--full"], cwd=ROOT, env=_env(), capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -47,12 +47,45 @@ def test_bench_one_gpu_contract(hip_lib):
     assert d["cg_sweeps"]["cg_sweep_bx"]["kernel"].startswith("k_cgA<")  # the fold sweep
 
 
+def test_bench_plain_run_dumps_outputs(hip_lib, tmp_path):
+    """A plain run (no --full) measures nothing after its timed steps: the
+    keys of the side measurements are null. --dump-outputs writes the fields
+    the last timed step left: at 17^3, Re 100, dt 5e-4, 1 warm-up + 2 timed
+    steps are the three steps of the oracle's cavity17_cg_3steps fixture, to
+    test_gpu_golden's 1e-10 for this CG path."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--size", "17", "--re", "100",
+                        "--dt", "5e-4", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(out)], cwd=ROOT, env=_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    d = _last_json(r.stdout)
+    assert KEYS <= set(d)
+    assert d["full"] is False and d["steps"] == 2 and d["value"] > 0 and d["dtype"] == "f64"
+    assert len(d["step_ms"]) == 2 and d["ms_per_step"] > 0
+    for k in ("cpu_baseline", "plugin_step", "cg_variant_compare", "cg_fixed200"):
+        assert d[k] is None, k
+    # the roofline on the timed steps' own timers stays, the stream roof is --full's
+    assert d["roofline"]["bound"] == "hbm" and d["roofline"]["achieved"] > 0
+    assert d["roofline"]["stream_copy_GBps"] is None
+    z = np.load(ROOT / "tests" / "golden" / "cavity17_cg_3steps.npz", allow_pickle=False)
+    assert all(abs(a - b) <= 1 for a, b in zip(d["cg_iters_per_step"], z["iters"][1:]))
+    assert sorted(p.name for p in out.iterdir()) == ["p.npy", "u.npy", "v.npy", "w.npy"]
+    for k in ("u", "v", "w", "p"):
+        a = np.load(out / f"{k}.npy", allow_pickle=False)
+        assert a.dtype == np.float64 and a.shape == (17, 17, 17)
+        rel = float(np.max(np.abs(a - z[k]))) / max(1.0, float(np.max(np.abs(z[k]))))
+        assert rel <= 1e-10, (k, rel)
+
+
 def test_bench_512_single_reduction_default(hip_lib):
     """At 512^3 on one GPU the default CG is the single-reduction z-march
     (bench.cg_variant_auto); its line carries k_ccf's roofline and the textbook
     iteration beside it."""
     r = subprocess.run([sys.executable, "bench.py", "--size", "512", "--steps", "1", "--warmup",
-                        "0", "--no-cpu-baseline"], cwd=ROOT, env=_env(), capture_output=True,
+                        "0", "--no-cpu-baseline", "--full"], cwd=ROOT, env=_env(), capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -99,7 +132,7 @@ def test_bench_multi_rank_rehearsal(hip_lib, case, world, size, cgv, probe):
            "--rdzv-backend=c10d", "--rdzv-endpoint=127.0.0.1:0", "--local-addr=127.0.0.1",
            "bench.py", "--gpus", str(world),
            "--size", str(size), "--steps", "2", "--warmup", "1", "--case", case,
-           "--cg-variant", str(cgv), "--cg-probe", probe]
+           "--cg-variant", str(cgv), "--cg-probe", probe, "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)

@@ -39,6 +39,17 @@ def _fixture():
     return json.loads(f.read_text())
 
 
+def _planes(step):
+    """The committed plane samples after `step`, one file per sampled plane k
+    (cavity512_re1000_step<s>_k<kz>_planes.npz) merged into one dict; None
+    for a step without them."""
+    out = {}
+    for f in sorted(GOLD.glob(f"cavity{N}_re1000_step{step}_k*_planes.npz")):
+        with np.load(f) as z:
+            out.update({key: z[key] for key in z.files})
+    return out or None
+
+
 def _interior_norms(a):
     import torch
     t = torch.from_numpy(a)[1:-1, 1:-1, 1:-1]
@@ -71,7 +82,7 @@ def check_step(row, iters, res0, res, vmax, pmax, field, worst):
     assert res == pytest.approx(row["final_residual"], rel=1e-4)
     assert vmax == pytest.approx(row["max_velocity"], rel=REL)
     assert pmax == pytest.approx(row["max_pressure"], rel=REL)
-    snap = GOLD / f"cavity{N}_re1000_step{row['step']}_planes.npz"
+    z = _planes(row["step"])
     for k in FIDS:
         a = field(k)
         l2, mx = _interior_norms(a)
@@ -79,8 +90,7 @@ def check_step(row, iters, res0, res, vmax, pmax, field, worst):
         worst["norm_rel"] = max(worst["norm_rel"], abs(l2 - ol2) / ol2, abs(mx - omx) / omx)
         assert l2 == pytest.approx(ol2, rel=REL, abs=1e-300), (row["step"], k)
         assert mx == pytest.approx(omx, rel=REL, abs=1e-300), (row["step"], k)
-        if snap.exists():
-            z = np.load(snap)
+        if z is not None:
             for kz in (1, 255, 510):
                 pre = f"{k}_k{kz}_"
                 plane = a[kz]
@@ -339,7 +349,8 @@ def test_cavity512_rccl_vs_oracle(hip_lib, tmp_path, world, cgv, nsteps):
     # the sampled planes, from the rank that owns each
     planes = np.load(tmp_path / "rccl512_planes.npz")
     for st in psteps:
-        z = np.load(GOLD / f"cavity{N}_re1000_step{st}_planes.npz")
+        z = _planes(st)
+        assert z is not None, st
         for k in FIDS:
             omx = rec["steps"][st - 1]["norms"][k][1]
             for kz in (1, 255, 510):

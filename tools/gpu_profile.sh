@@ -6,11 +6,11 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${TAG:-p1}
 N=${N:-512}
-ARGS=${ARGS:-"--size $N --steps 1 --warmup 1 --no-cpu-baseline"}
+ARGS=${ARGS:-"--size $N --steps 1 --warmup 1 --full --no-cpu-baseline"}
 # interior cells per launch the traffic is divided by (bench.py keys the
 # profile on it): (N-2)^3 for the cavity; the convection case passes its own
 CELLS=${CELLS:-$(( (N-2)*(N-2)*(N-2) ))}
-OUT=gpurun_out/prof_${TAG}
+OUT=${OUT_DIR:-bench_out}/prof_${TAG}
 mkdir -p $OUT
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
     python3 bench.py $ARGS > $OUT/bench_trace.log 2>&1

@@ -33,7 +33,8 @@ import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
-REF = Path("/root/reference")
+# the reference checkout: CFD_REFERENCE_DIR, else `reference` beside this repository
+REF = Path(os.environ.get("CFD_REFERENCE_DIR") or ROOT.parent / "reference")
 
 
 def edit(path: Path, anchor: str, insert: str, after: bool = True) -> None:
@@ -102,7 +103,7 @@ def main():
     ap.add_argument("--jobs", type=int, default=8)
     a = ap.parse_args()
     if not REF.is_dir():
-        raise SystemExit("reference_link: /root/reference is absent")
+        raise SystemExit(f"reference_link: {REF} is absent")
     hip = ROOT / "cfd_amd/lib/libcfd_hip.so"
     if not hip.exists():
         raise SystemExit("reference_link: build libcfd_hip.so first (make -C cfd_amd/csrc)")
