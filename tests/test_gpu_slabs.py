@@ -200,15 +200,22 @@ def test_slab_taylor_green_vs_oracle(hip_lib, nranks, n):
         assert float(np.max(np.abs(got[k] - ref))) / scale <= 1e-10, k
 
 
-def _slab_poisson(g, rhs, nranks, method, prm=None, check_halo=False, **cfg):
+def _slab_poisson(g, rhs, nranks, method, prm=None, check_halo=False, x0=None, stats=None,
+                  **cfg):
+    """x0 (optional): the initial iterate on the whole grid, each rank taking
+    its slab with both halo planes; zero without it. stats (optional): a list
+    that receives every rank's PoissonStats, in rank order."""
     S = Slabs(g, nranks, **cfg)
     try:
         def body(r, c):
             sl = slice(c.k_offset, c.k_offset + c.nz_local)
-            x = np.zeros(c.shape)
+            x = np.zeros(c.shape) if x0 is None else np.array(x0[sl])  # a copy
             s, st = c.poisson_solve(method, x, rhs[sl], g.dx, g.dy, g.dz, prm)
-            return s, st.iterations, x
+            return s, st.iterations, x, st
         res = S.run(body)
+        if stats is not None:
+            stats.extend(r[3] for r in res)
+        res = [r[:3] for r in res]
         x = np.full(rhs.shape, np.nan)
         for c, (s, it, xl) in zip(S.ctx, res):
             loc, glob = c.owned()
