@@ -226,6 +226,11 @@ def _bind_hip(lib) -> None:
     _sig(lib, "hip_rk4_step_device", C.c_int, V, P(A.Grid), P(A.SolverParams), P(A.SolverStats))
     _sig(lib, "hip_rk4_step", C.c_int, V, P(A.FlowField), P(A.Grid), P(A.SolverParams),
          P(A.SolverStats))
+    for integ in ("rk2", "euler"):
+        _sig(lib, f"hip_{integ}_step_device", C.c_int, V, P(A.Grid), P(A.SolverParams),
+             P(A.SolverStats))
+        _sig(lib, f"hip_{integ}_step", C.c_int, V, P(A.FlowField), P(A.Grid), P(A.SolverParams),
+             P(A.SolverStats))
     _sig(lib, "create_projection_hip_solver", P(A.NSSolver))
     _sig(lib, "create_rk4_hip_solver", P(A.NSSolver))
     _sig(lib, "cfd_hip_register_solvers", None, V)
@@ -262,8 +267,9 @@ def _bind_hip(lib) -> None:
          P(A.GpuConfig))
     _sig(lib, "solve_projection_method_gpu", C.c_int, P(A.FlowField), P(A.Grid),
          P(A.SolverParams), P(A.GpuConfig))
-    _sig(lib, "solve_rk4_method_gpu", C.c_int, P(A.FlowField), P(A.Grid), P(A.SolverParams),
-         P(A.GpuConfig))
+    for name in ("solve_rk4_method_gpu", "solve_rk2_method_gpu",
+                 "solve_explicit_euler_method_gpu"):
+        _sig(lib, name, C.c_int, P(A.FlowField), P(A.Grid), P(A.SolverParams), P(A.GpuConfig))
 
 
 def _import_torch_first() -> None:

@@ -512,6 +512,42 @@ class HipProjection:
         return self._lib().hip_proj_step_device(self._ctx, grid.ptr, C.byref(params),
                                                 C.byref(st))
 
+    def _integrator_step(self, name: str, field, grid, params, stats) -> int:
+        st = stats if stats is not None else A.SolverStats()
+        if field is None:
+            return getattr(self._lib(), f"hip_{name}_step_device")(
+                self._ctx, grid.ptr, C.byref(params), C.byref(st))
+        return getattr(self._lib(), f"hip_{name}_step")(self._ctx, field.ptr, grid.ptr,
+                                                        C.byref(params), C.byref(st))
+
+    def rk4_step(self, field: FlowField, grid: Grid, params: A.SolverParams,
+                 stats: Optional[A.SolverStats] = None) -> int:
+        """hip_rk4_step: upload, one RK4 step (rk4_impl, bitwise), download."""
+        return self._integrator_step("rk4", field, grid, params, stats)
+
+    def rk4_step_device(self, grid: Grid, params: A.SolverParams,
+                        stats: Optional[A.SolverStats] = None) -> int:
+        return self._integrator_step("rk4", None, grid, params, stats)
+
+    def rk2_step(self, field: FlowField, grid: Grid, params: A.SolverParams,
+                 stats: Optional[A.SolverStats] = None) -> int:
+        """hip_rk2_step: upload, one RK2 (Heun) step (rk2_impl, bitwise), download."""
+        return self._integrator_step("rk2", field, grid, params, stats)
+
+    def rk2_step_device(self, grid: Grid, params: A.SolverParams,
+                        stats: Optional[A.SolverStats] = None) -> int:
+        return self._integrator_step("rk2", None, grid, params, stats)
+
+    def euler_step(self, field: FlowField, grid: Grid, params: A.SolverParams,
+                   stats: Optional[A.SolverStats] = None) -> int:
+        """hip_euler_step: upload, one explicit Euler step (explicit_euler_impl,
+        bitwise; advances with min(dt, 1e-4)), download."""
+        return self._integrator_step("euler", field, grid, params, stats)
+
+    def euler_step_device(self, grid: Grid, params: A.SolverParams,
+                          stats: Optional[A.SolverStats] = None) -> int:
+        return self._integrator_step("euler", None, grid, params, stats)
+
     def set_field(self, fid: int, arr: np.ndarray):
         a = np.ascontiguousarray(arr, dtype=np.float64)
         assert a.shape == self.shape, (a.shape, self.shape)

@@ -28,6 +28,12 @@ extern "C" __attribute__((visibility("hidden"))) cfd_status_t hip_proj_step_iter
 extern "C" __attribute__((visibility("hidden"))) cfd_status_t hip_rk4_step_iter_internal(
     hip_proj_ctx_t* c, flow_field* f, const grid* g, const ns_solver_params_t* prm,
     ns_solver_stats_t* stats, int n_steps);
+extern "C" __attribute__((visibility("hidden"))) cfd_status_t hip_rk2_step_iter_internal(
+    hip_proj_ctx_t* c, flow_field* f, const grid* g, const ns_solver_params_t* prm,
+    ns_solver_stats_t* stats, int n_steps);
+extern "C" __attribute__((visibility("hidden"))) cfd_status_t hip_euler_step_iter_internal(
+    hip_proj_ctx_t* c, flow_field* f, const grid* g, const ns_solver_params_t* prm,
+    ns_solver_stats_t* stats, int n_steps);
 
 namespace {
 
@@ -382,33 +388,41 @@ cfd_status_t solve_projection_method_gpu(flow_field* field, const grid* g,
     return s;
 }
 
-static cfd_status_t not_on_path(const char* what) {
-    set_err(CFD_ERROR_UNSUPPORTED, what);
-    return CFD_ERROR_UNSUPPORTED;
-}
-
-cfd_status_t solve_explicit_euler_method_gpu(flow_field*, const grid*, const ns_solver_params_t*,
-                                             const gpu_config_t*) {
-    return not_on_path("GPU explicit Euler solver: not provided by the MI355X projection library");
-}
-
-cfd_status_t solve_rk2_method_gpu(flow_field*, const grid*, const ns_solver_params_t*,
-                                  const gpu_config_t*) {
-    return not_on_path("GPU RK2 solver: not provided by the MI355X projection library");
-}
-
-cfd_status_t solve_rk4_method_gpu(flow_field* field, const grid* g,
-                                  const ns_solver_params_t* params, const gpu_config_t* config) {
-    // solver_rk_gpu.cu:260-553 (order 4): params->max_iter RK4 steps
+// The explicit integrators' entries: the gpu_should_use gate, a temporary
+// context, params->max_iter steps (source index 0 .. max_iter - 1).
+typedef cfd_status_t (*step_iter_fn)(hip_proj_ctx_t*, flow_field*, const grid*,
+                                     const ns_solver_params_t*, ns_solver_stats_t*, int);
+static cfd_status_t solve_integrator(step_iter_fn steps, flow_field* field, const grid* g,
+                                     const ns_solver_params_t* params,
+                                     const gpu_config_t* config) {
     if (!field || !g || !params) return CFD_ERROR_INVALID;
     gpu_config_t cfg = config ? *config : gpu_config_default();
     if (!gpu_should_use(&cfg, field->nx, field->ny, field->nz, params->max_iter)) return CFD_ERROR;
     hip_proj_config_t pcfg = hip_proj_config_default();
     hip_proj_ctx_t* pc = hip_proj_create(field->nx, field->ny, field->nz, &pcfg);
     if (!pc) return CFD_ERROR_NOMEM;
-    cfd_status_t s = hip_rk4_step_iter_internal(pc, field, g, params, nullptr, params->max_iter);
+    cfd_status_t s = steps(pc, field, g, params, nullptr, params->max_iter);
     hip_proj_destroy(pc);
     return s;
+}
+
+cfd_status_t solve_explicit_euler_method_gpu(flow_field* field, const grid* g,
+                                             const ns_solver_params_t* params,
+                                             const gpu_config_t* config) {
+    // params->max_iter steps of explicit_euler_impl (solver_explicit_euler.c:337-582)
+    return solve_integrator(hip_euler_step_iter_internal, field, g, params, config);
+}
+
+cfd_status_t solve_rk2_method_gpu(flow_field* field, const grid* g,
+                                  const ns_solver_params_t* params, const gpu_config_t* config) {
+    // params->max_iter steps of rk2_impl (solver_rk2.c:48-211)
+    return solve_integrator(hip_rk2_step_iter_internal, field, g, params, config);
+}
+
+cfd_status_t solve_rk4_method_gpu(flow_field* field, const grid* g,
+                                  const ns_solver_params_t* params, const gpu_config_t* config) {
+    // solver_rk_gpu.cu:260-553 (order 4): params->max_iter RK4 steps
+    return solve_integrator(hip_rk4_step_iter_internal, field, g, params, config);
 }
 
 }  // extern "C"

@@ -1767,7 +1767,8 @@ template <bool BUOY, class Diffs>
 __device__ __forceinline__ void rk_pair_kr(const RkCoef& rc, Diffs diffs, double2 uc, double2 vc,
                                            double2 wc, double2 r2, double2 t2, double su,
                                            double sv0, double sv1, bool oka, bool okb,
-                                           double (&kra)[4], double (&krb)[4]) {
+                                           double (&kra)[4], double (&krb)[4],
+                                           double* div2 = nullptr) {
     RkD1 pa_, pb_;
     diffs(3, pa_, pb_);
     const double dpxa = clampl(pa_.dx, 100.0), dpya = clampl(pa_.dy, 100.0),
@@ -1810,6 +1811,10 @@ __device__ __forceinline__ void rk_pair_kr(const RkCoef& rc, Diffs diffs, double
     }
     if (oka) kra[3] = -0.1 * r2.x * fmax(-10.0, fmin(10.0, diva));
     if (okb) krb[3] = -0.1 * r2.y * fmax(-10.0, fmin(10.0, divb));
+    if (div2) {  // the clamped divergence itself (k_euler_step scales it by dt)
+        div2[0] = fmax(-10.0, fmin(10.0, diva));
+        div2[1] = fmax(-10.0, fmin(10.0, divb));
+    }
 }
 
 // The stage update of one pair of field q (solver_rk4.c stage sums): stage
@@ -1894,6 +1899,76 @@ __global__ __launch_bounds__(256) void k_rk_stage2(Geo g, RkCoef rc, Fld4 cur, F
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) rk_pair_update<STAGE>(rc, q0, acc, out, q, idx, kra[q], krb[q]);
+}
+
+// ---------------------------------------------------------------------------
+// Explicit Euler (solver_explicit_euler.c:391-525): the whole update of u, v,
+// w, p in one pass on k_rk_stage2's x pairs (128 columns x 4 rows per
+// workgroup, 16-B loads and stores). The momentum expressions are the RK
+// RHS's (rk_pair_kr); what differs from an RK stage:
+//   - the stencil reads the ghost cells: neighbours are idx +- 1, +- px,
+//     +- sz by address, no periodic index resolution (2-D: sz = 0);
+//   - the increments rc.fac * k (rc.fac = min(dt, 1e-4)) are clamped to +-1
+//     before they are added, u, v, w then to +-100;
+//   - dp = -0.1 * fac * rho * clamp(div, +-10), clamped to +-1;
+//   - boundary cells and the cells the reference skips (rho <= 1e-10 or a
+//     spacing below 1e-10) keep their values: every cell of `out` is written,
+//     so the caller swaps cur and out.
+// Per cell: reads u, v, w, p, rho (and T with buoyancy), writes u, v, w, p:
+// 72 / 80 B of algorithmic traffic.
+// ---------------------------------------------------------------------------
+template <bool BUOY>
+__global__ __launch_bounds__(256) void k_euler_step(Geo g, RkCoef rc, Fld4 cur, Fld4 out,
+                                                    const double* __restrict__ rho,
+                                                    const double* __restrict__ T,
+                                                    const double* __restrict__ dxa,
+                                                    const double* __restrict__ dya,
+                                                    const double* __restrict__ su_row,
+                                                    const double* __restrict__ sv_col) {
+    const int i0 = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
+    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int k = blockIdx.z;
+    if (i0 >= g.nx || j >= g.ny) return;
+    const long long idx = cidx(g, i0, j, k);
+    const bool rowin = (j >= 1 && j <= g.ny - 2 && k >= g.k0 && k < g.k1);
+    const bool ina = rowin && i0 >= 1 && i0 <= g.nx - 2;
+    const bool inb = rowin && i0 + 1 <= g.nx - 2;
+    double2 o[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = ld2(cur.f[q], idx);
+    if (ina || inb) {
+        const long long jd = idx - g.px, ju = idx + g.px;
+        const long long kd = idx - g.sz, ku = idx + g.sz;  // 2-D: sz = 0, z terms vanish
+        const double2 r2 = ld2(rho, idx);
+        const double2 t2 = BUOY ? ld2(T, idx) : make_double2(0.0, 0.0);
+        const double dyj = dya[j], su = su_row[j];
+        const double dxa0 = dxa[i0], dxa1 = dxa[min(i0 + 1, g.nx - 1)];
+        const bool oka = ina && !(r2.x <= 1e-10) && !(fabs(dxa0) < 1e-10) && !(fabs(dyj) < 1e-10);
+        const bool okb = inb && !(r2.y <= 1e-10) && !(fabs(dxa1) < 1e-10) && !(fabs(dyj) < 1e-10);
+        auto diffs = [&](int f, RkD1& da, RkD1& db) __attribute__((always_inline)) {
+            const double* F = cur.f[f];
+            const double2 c2 = ld2(F, idx), d2 = ld2(F, jd), u2 = ld2(F, ju);
+            const double2 m2 = ld2(F, kd), p2 = ld2(F, ku);
+            // x neighbours outside the pair; a cell that needs one is interior,
+            // so i0 - 1 >= 0 and i0 + 2 <= nx - 1 where the value is used
+            const double xl = ina ? F[idx - 1] : 0.0;
+            const double xr = inb ? F[idx + 2] : 0.0;
+            rk_pair_diffs(rc, c2, d2, u2, m2, p2, xl, c2.y, c2.x, xr, dxa0, dxa1, dyj, da, db);
+        };
+        double kra[4] = {0.0, 0.0, 0.0, 0.0}, krb[4] = {0.0, 0.0, 0.0, 0.0};
+        double div2[2] = {0.0, 0.0};
+        rk_pair_kr<BUOY>(rc, diffs, o[0], o[1], o[2], r2, t2, su, sv_col[i0],
+                         sv_col[min(i0 + 1, g.nx - 1)], oka, okb, kra, krb, div2);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (oka) o[q].x = clampl(o[q].x + clampl(rc.fac * kra[q], 1.0), 100.0);
+            if (okb) o[q].y = clampl(o[q].y + clampl(rc.fac * krb[q], 1.0), 100.0);
+        }
+        if (oka) o[3].x = o[3].x + clampl(-0.1 * rc.fac * r2.x * div2[0], 1.0);
+        if (okb) o[3].y = o[3].y + clampl(-0.1 * rc.fac * r2.y * div2[1], 1.0);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) st2(out.f[q], idx, o[q]);
 }
 
 // max |u|, max |p| and the non-finite flag over the owned planes (the

@@ -22,8 +22,10 @@
  * reference's explicit pressure-relaxation step (solver_projection_gpu.cu:523-570)
  * as two fused HIP sweeps + boundary gathers, and `solve_projection_method_gpu`
  * runs the Chorin projection of projection_hip with the reference GPU's
- * solver settings (see the function comment). solve_rk2_method_gpu is not
- * provided (RK2 is outside the projection path).
+ * solver settings (see the function comment). solve_rk4_method_gpu,
+ * solve_rk2_method_gpu and solve_explicit_euler_method_gpu run params->max_iter
+ * steps whose fields are bitwise those of the CPU scalar solvers rk4_impl,
+ * rk2_impl and explicit_euler_impl (per-index dx[], dy[] accepted).
  */
 #ifndef CFD_HIP_GPU_DEVICE_H
 #define CFD_HIP_GPU_DEVICE_H
@@ -110,10 +112,11 @@ CFD_HIP_EXPORT cfd_status_t solve_projection_method_gpu(flow_field* field, const
 CFD_HIP_EXPORT cfd_status_t solve_rk4_method_gpu(flow_field* field, const grid* grid,
                                                  const ns_solver_params_t* params,
                                                  const gpu_config_t* config);
-/* solver_rk_gpu.cu:535-545 integrators outside the projection path: they
- * return CFD_ERROR_UNSUPPORTED. Exported so that libcfd_hip.so defines every
- * symbol of the reference's no-CUDA stub (solver_gpu_stub.c:15-161): a link
- * that names libcfd_hip.so before libcfd_core.a then never pulls the stub's
+/* solver_rk_gpu.cu:535-545: params->max_iter explicit Euler / RK2 (Heun)
+ * steps, bitwise explicit_euler_impl (solver_explicit_euler.c:337-582) and
+ * rk2_impl (solver_rk2.c:48-211). With these libcfd_hip.so defines and serves
+ * every symbol of the reference's no-CUDA stub (solver_gpu_stub.c:15-161): a
+ * link that names libcfd_hip.so before libcfd_core.a never pulls the stub's
  * object in. */
 CFD_HIP_EXPORT cfd_status_t solve_explicit_euler_method_gpu(flow_field* field, const grid* grid,
                                                             const ns_solver_params_t* params,

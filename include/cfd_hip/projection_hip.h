@@ -144,7 +144,8 @@ typedef enum {
     HIP_KT_RELAX = 5,      /* one RB-SOR colour pass or one Jacobi sweep */
     HIP_KT_RESIDUAL = 6,   /* L-infinity residual for the relaxation methods */
     HIP_KT_ENERGY = 7,     /* energy equation (alpha > 0) */
-    HIP_KT_RK_STAGE = 8,   /* one fused RK4 stage (RHS + stage update) */
+    HIP_KT_RK_STAGE = 8,   /* one fused RK4 / RK2 stage (RHS + stage update), or the
+                              explicit Euler step kernel */
     HIP_KT_CG_SWEEP_BX = 9,/* every 4th iteration: sweep A + x += alpha p of the previous 4 */
     HIP_KT_CC_UPDATE = 10, /* cg_variant 1: p, s, r (and the x fold) update */
     HIP_KT_CC_SPMV = 11,   /* cg_variant 1: w = A r + (r,r), (w,r) */
@@ -449,6 +450,27 @@ CFD_HIP_EXPORT cfd_status_t hip_rk4_step_device(hip_proj_ctx_t* ctx, const grid*
 CFD_HIP_EXPORT cfd_status_t hip_rk4_step(hip_proj_ctx_t* ctx, flow_field* field, const grid* g,
                                          const ns_solver_params_t* params,
                                          ns_solver_stats_t* stats);
+
+/* ---- RK2 (solver_rk2.c:48-211) and explicit Euler --------------------------
+ * (solver_explicit_euler.c:337-582). Same contract as the RK4 pair above: one
+ * step of the reference's CPU scalar solver on a context's fields, every field
+ * bitwise; stats->iterations = 1, max velocity / pressure / temperature.
+ * RK2 (Heun) uses the RK4 stage kernels (no BCs between the stages). Explicit
+ * Euler reads the ghost cells (no periodic index resolution), advances with
+ * min(dt, 1e-4), clamps each increment to +-1 and leaves the boundary cells of
+ * u, v, w to the caller; p, rho, T get the periodic copies. */
+CFD_HIP_EXPORT cfd_status_t hip_rk2_step_device(hip_proj_ctx_t* ctx, const grid* g,
+                                                const ns_solver_params_t* params,
+                                                ns_solver_stats_t* stats);
+CFD_HIP_EXPORT cfd_status_t hip_rk2_step(hip_proj_ctx_t* ctx, flow_field* field, const grid* g,
+                                         const ns_solver_params_t* params,
+                                         ns_solver_stats_t* stats);
+CFD_HIP_EXPORT cfd_status_t hip_euler_step_device(hip_proj_ctx_t* ctx, const grid* g,
+                                                  const ns_solver_params_t* params,
+                                                  ns_solver_stats_t* stats);
+CFD_HIP_EXPORT cfd_status_t hip_euler_step(hip_proj_ctx_t* ctx, flow_field* field, const grid* g,
+                                           const ns_solver_params_t* params,
+                                           ns_solver_stats_t* stats);
 
 /* ---- plugin surface ------------------------------------------------------ */
 CFD_HIP_EXPORT ns_solver_t* create_projection_hip_solver(void);
