@@ -24,11 +24,13 @@
 //   a: p_it at plane q + 2 from the loaded r_it, p_{it-1}  (published in LDS)
 //   b: s_it and r_{it+1} at plane q + 1: in-plane p from LDS, z from the
 //      lane's ring; p_it and r_{it+1} stored there (published in LDS)
-//   c: w_{it+1} at plane q and the two dot products
+//   c: w_{it+1} at plane q and the two dot products (one device: delta as a
+//      sum over grid edges, no w; see ccf_body)
 // one barrier per step; LDS holds p_it and r_{it+1} planes by parity.
 //
 // Tiles: 32 x pairs (64 columns) x 32 rows, 1024 threads, lane l of wave w
-// owns pair l % 32 of rows w and w + 16; 60 x 28 cells written per tile.
+// owns pair l % 32 of rows w and w + 16; 60 x 28 cells written per tile
+// (60 x 29 in the edge-sum form, whose halo is one cell on the minus side).
 #pragma once
 
 #include "kernels.hpp"
@@ -90,6 +92,7 @@ constexpr int CCF_TC = 32;  // x pairs per tile row
 constexpr int CCF_TR = 32;  // tile rows
 constexpr int CCF_OX = 60;  // columns written per tile
 constexpr int CCF_OY = 28;  // rows written per tile
+constexpr int CCF_OY_EDGE = 29;  // ... in the edge-sum form (ccf_body EDGE)
 // LDS plane: rows of 2 padded halves (.x cells, then .y cells) so that an x
 // neighbour (one double of the adjacent lane) is a conflict-free 8-B read
 constexpr int CCF_LP = CCF_TC + 2;
@@ -110,14 +113,36 @@ struct CcfLds {
 // neighbours the march forms itself (the edge planes' r_{it+1} from the same
 // operands as the edge launch), and its partial dot products join the edge
 // planes' k_cc2 launch (g.part_ofs / part_total, dist = 1).
-template <bool FIRST, bool FOLD, bool NOC = false>
-static __global__ __launch_bounds__(1024, 4) void k_ccf(
-    SGeo g, Lap Lp, const double* __restrict__ R0, double* __restrict__ R1,
+//
+// EDGE (one device, kmode 0; the kernel k_ccf<.., false>): stage c forms
+// delta = (r, A r) as a sum over grid edges instead of w = A r at every cell.
+// A = -lap7 with zero walls is symmetric, so
+//   (r, A r) = sum over the edges (i, i + e), wall edges included, of
+//              c_dir (r_i - r_{i+e})^2,   c = dx2_inv, dy2_inv, inv_dz2
+// and every owned interior cell adds its three plus-side edges (masked cells
+// hold r = 0, so the plus-side walls are ordinary edges) and c_dir r_i^2 for
+// each minus-side wall it touches (i, j or k equal to 1). r_{it+1} is then
+// needed on the owned cells and their plus-side face neighbours only: the
+// halo is one cell on the minus side and two on the plus side, the loaded
+// 64 x 32 tile writes 60 x 29 cells (row origin ty 29 - 1; rows 1..29 owned),
+// and a z run loads planes kb - 1 .. ke + 1 and takes ke - kb + 3 steps.
+// r_{it+1} of plane kb - 1, row 0, row 31 and pair 0 .x / pair 31 .y is formed
+// from operands the tile does not hold and feeds nothing. The sum differs
+// from (w, r) in rounding only (its terms are non-negative). Z-slabs keep
+// the cell form (!EDGE): the interior march shares its reduction with k_cc2's
+// (w, r) of the edge planes, and the two forms' partial sums do not add up.
+template <bool FIRST, bool FOLD, bool NOC, bool EDGE>
+static __device__ __forceinline__ void ccf_body(
+    const SGeo& g, const Lap& Lp, const double* __restrict__ R0, double* __restrict__ R1,
     const double* __restrict__ Po, double* __restrict__ Pn, PPrev pv, double* __restrict__ x,
     CgState* st, double* partials, unsigned* counter, int it, int xmap, int dist, double* dsum,
     Mbox* mb, unsigned long long* clk) {
     // (a fold step reads p_{it-1} from the po ring, which FIRST never loads)
     static_assert(!(FIRST && FOLD), "k_ccf: no fold in the first iteration");
+    static_assert(!(NOC && EDGE), "k_ccf: the edge sum is stage c's");
+    constexpr int OY = EDGE ? CCF_OY_EDGE : CCF_OY;  // rows written per tile
+    constexpr int RLO = EDGE ? 1 : 2;                // first owned tile row
+    constexpr int ZPRO = EDGE ? 3 : 4;               // steps ahead of plane kb
     __shared__ CcfLds L;
     if (CCF_DIAG == 0 && st->done) return;
     // clock sample (clk != nullptr on one launch in eight while the context
@@ -147,7 +172,7 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
     const int c = lane & 31;
     const int r = w + 16 * (lane >> 5);
     const int i0 = tx * CCF_OX - 2 + 2 * c;  // even; the pair is (i0, i0 + 1)
-    const int j = ty * CCF_OY - 2 + r;
+    const int j = ty * OY - RLO + r;
     // kmode 1 (Z-slabs, NOC): the slab's two edge planes (tz 0 -> k0, tz 1 ->
     // k1 - 1); kmode 2: the planes [kt0, kt1) between them
     int kb, ke;
@@ -168,8 +193,9 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
     const bool jin = j >= 1 && j <= g.ny - 2;
     const bool in0 = jin && i0 >= 1 && i0 <= g.nx - 2;
     const bool in1 = jin && i0 + 1 >= 1 && i0 + 1 <= g.nx - 2;
-    // written / reduced: pairs 1..30 of rows 2..29 that hold a grid pair
-    const bool own = c >= 1 && c <= CCF_TC - 2 && r >= 2 && r <= CCF_TR - 3;
+    // written / reduced: pairs 1..30 of rows 2..29 (EDGE: 1..29) that hold a
+    // grid pair
+    const bool own = c >= 1 && c <= CCF_TC - 2 && r >= RLO && r <= CCF_TR - 3;
     const bool wr = own && jin && i0 >= 0 && i0 < g.nx;
     // loads from always-valid addresses: outside the grid they hold other
     // cells' values, which only feed cells outside the interior (masked)
@@ -228,18 +254,26 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
             stencil_n(nbrs(pl), v, zm, zp, out);
         }
     };
-    const int q0 = kb - 4;  // steps q0 .. ke - 1 (see the header)
-    const int nsteps = ke - kb + 4;
+    const int q0 = kb - ZPRO;  // steps q0 .. ke - 1 (see the header)
+    const int nsteps = ke - kb + ZPRO;
+    // EDGE: the minus-side wall edges of the lane's cells, c_dir r^2 (i == 1
+    // is always a pair's .y: i0 is even); the k == 1 edge joins per step
+    const double wal0 = (EDGE && j == 1) ? Lp.dy2_inv : 0.0;
+    const double wal1 = (EDGE && i0 == 0) ? wal0 + Lp.dx2_inv : wal0;
     // rings (slot of plane p at step q: (p - q0) & 3): r_it, p_{it-1} (loaded
-    // one step ahead), p_it, r_{it+1}; fold operands (x, p_{it-3..it-1}) by parity
-    double2 rr[4], po[4], pn[4], rn[4];
+    // one step ahead), p_it, r_{it+1} (EDGE: planes q and q + 1 only, by
+    // parity); fold operands (x, p_{it-3..it-1}) by parity
+    constexpr int RNM = EDGE ? 1 : 3;
+    double2 rr[4], po[4], pn[4], rn[RNM + 1];
     double2 fx[2], f0[2], f1[2];
     const double2 zero = make_double2(0.0, 0.0);
 #pragma unroll
-    for (int s = 0; s < 4; ++s) pn[s] = rn[s] = po[s] = rr[s] = zero;
+    for (int s = 0; s < 4; ++s) pn[s] = po[s] = rr[s] = zero;
+#pragma unroll
+    for (int s = 0; s <= RNM; ++s) rn[s] = zero;
     fx[0] = fx[1] = f0[0] = f0[1] = f1[0] = f1[1] = zero;
-    // (r_it of plane q0 + 1 = kb - 3 only feeds r_{it+1} there, never used)
-    // (the fold operands of plane q0 + 1 = kb - 3 are never stored: no load)
+    // (r_it of plane q0 + 1 = kb - 3 (EDGE: kb - 2) only feeds r_{it+1} there,
+    // never used; its fold operands are never stored: no load)
     // Each prologue load is followed by dropped stores in the place of a
     // step's stores, so that the first steps' waits for these loads count the
     // same ops as every later step's (the loop header joins both paths).
@@ -262,7 +296,8 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
     auto step = [&](auto Pc, int q) __attribute__((always_inline)) {
         constexpr int P = decltype(Pc)::value;
         constexpr int S0 = P & 3, S1 = (P + 1) & 3, S2 = (P + 2) & 3, S3 = (P + 3) & 3;
-        constexpr int SM = (P + 3) & 3;  // plane q - 1 (r_{it+1})
+        constexpr int SM = (P + 3) & 3;  // plane q - 1 (r_{it+1}, !EDGE)
+        constexpr int RS0 = P & RNM, RS1 = (P + 1) & RNM;  // r_{it+1} slots of q, q + 1
         constexpr int F1 = (P + 1) & 1, F2 = P & 1;  // fold slots of planes q + 1, q + 2
         constexpr int LPR = (P + 1) & 1, LPW = P & 1;        // p_it planes q + 1 (read), q + 2
         constexpr int LRR = 2 + (P & 1), LRW = 2 + ((P + 1) & 1);  // r_{it+1} q (read), q + 1
@@ -309,7 +344,12 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
         // stage c's in-plane operands (r_{it+1} of plane q, published last
         // step) first: their LDS latency then overlaps stages a and b
         Nb nc{};
-        if constexpr (!NOC && CCF_CFIRST) nc = nbrs(LRR);
+        if constexpr (!NOC && !EDGE && CCF_CFIRST) nc = nbrs(LRR);
+        if constexpr (EDGE && CCF_CFIRST) {
+            nc.rt = lrd(LRR, RTo);
+            nc.ux = lrd(LRR, UPX);
+            nc.uy = lrd(LRR, UPY);
+        }
         // ---- a: p_it at q + 2 ----
         const double2 p2 = FIRST ? rr[S2] : fma2p(rr[S2], beta, po[S2]);
         pn[S2] = p2;
@@ -321,15 +361,42 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
         const double2 rv = rr[S1];
         const double2 r1 = make_double2((kbin && in0) ? rv.x + ma * s.x : 0.0,
                                         (kbin && in1) ? rv.y + ma * s.y : 0.0);
-        rn[S1] = r1;
+        rn[RS1] = r1;
         if constexpr (!CCF_CFIRST) __builtin_amdgcn_sched_barrier(0);
         // ---- c: w_{it+1} at q, the dot products ----
-        if constexpr (!NOC) {
-            double2 wv;
-            if constexpr (CCF_CFIRST) stencil_n(nc, rn[S0], rn[SM], r1, wv);
-            else stencil(LRR, rn[S0], rn[SM], r1, wv);
+        if constexpr (EDGE) {
+            // the plus-side neighbours of the pair at plane q: +x is the
+            // lane's own .y / pair c + 1's .x, +y row r + 1 (both from the
+            // r_{it+1} plane published last step), +z this step's r1
+            if constexpr (!CCF_CFIRST && CCF_DIAG != 2) {
+                nc.rt = lrd(LRR, RTo);
+                nc.ux = lrd(LRR, UPX);
+                nc.uy = lrd(LRR, UPY);
+            }
             if (q >= kb && own) {
-                const double2 rc = rn[S0];
+                const double2 rc = rn[RS0];
+                const double walz = (q == 1) ? Lp.inv_dz2 : 0.0;
+                if (in0) {
+                    const double g2 = rc.x * rc.x;
+                    const double ex = rc.x - rc.y, ey = rc.x - nc.ux, ez = rc.x - r1.x;
+                    accg += g2;
+                    accd += ((Lp.dx2_inv * (ex * ex) + Lp.dy2_inv * (ey * ey)) +
+                             Lp.inv_dz2 * (ez * ez)) + (wal0 + walz) * g2;
+                }
+                if (in1) {
+                    const double g2 = rc.y * rc.y;
+                    const double ex = rc.y - nc.rt, ey = rc.y - nc.uy, ez = rc.y - r1.y;
+                    accg += g2;
+                    accd += ((Lp.dx2_inv * (ex * ex) + Lp.dy2_inv * (ey * ey)) +
+                             Lp.inv_dz2 * (ez * ez)) + (wal1 + walz) * g2;
+                }
+            }
+        } else if constexpr (!NOC) {
+            double2 wv;
+            if constexpr (CCF_CFIRST) stencil_n(nc, rn[RS0], rn[SM], r1, wv);
+            else stencil(LRR, rn[RS0], rn[SM], r1, wv);
+            if (q >= kb && own) {
+                const double2 rc = rn[RS0];
                 if (in0) {
                     accg += rc.x * rc.x;
                     accd += wv.x * rc.x;
@@ -409,6 +476,30 @@ static __global__ __launch_bounds__(1024, 4) void k_ccf(
                              (unsigned)g.part_ofs, (unsigned)g.part_total) &&
         threadIdx.x == 0)
         cc_reduce_finish(st, tg, td, it, false, dist != 0, mb, dsum);
+}
+
+// One device (kmode 0): the edge-sum form; NOC: a Z-slab's edge planes.
+template <bool FIRST, bool FOLD, bool NOC = false>
+static __global__ __launch_bounds__(1024, 4) void k_ccf(
+    SGeo g, Lap Lp, const double* __restrict__ R0, double* __restrict__ R1,
+    const double* __restrict__ Po, double* __restrict__ Pn, PPrev pv, double* __restrict__ x,
+    CgState* st, double* partials, unsigned* counter, int it, int xmap, int dist, double* dsum,
+    Mbox* mb, unsigned long long* clk) {
+    ccf_body<FIRST, FOLD, NOC, !NOC>(g, Lp, R0, R1, Po, Pn, pv, x, st, partials, counter, it, xmap,
+                                     dist, dsum, mb, clk);
+}
+
+// The cell form w = A r with stage c (60 x 28 tiles, 4-step z prologue): a
+// Z-slab's interior planes (kmode 2), and one device under
+// CFD_HIP_CCF_EDGE_DOT=0.
+template <bool FIRST, bool FOLD>
+static __global__ __launch_bounds__(1024, 4) void k_ccf_cell(
+    SGeo g, Lap Lp, const double* __restrict__ R0, double* __restrict__ R1,
+    const double* __restrict__ Po, double* __restrict__ Pn, PPrev pv, double* __restrict__ x,
+    CgState* st, double* partials, unsigned* counter, int it, int xmap, int dist, double* dsum,
+    Mbox* mb, unsigned long long* clk) {
+    ccf_body<FIRST, FOLD, false, false>(g, Lp, R0, R1, Po, Pn, pv, x, st, partials, counter, it,
+                                        xmap, dist, dsum, mb, clk);
 }
 
 }  // namespace cfdhip

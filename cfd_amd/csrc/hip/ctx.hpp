@@ -145,6 +145,7 @@ struct hip_proj_ctx {
     // k_cc2's tiling of the two edge planes completing it (tiles_x 0: off)
     SGeo cc_int_red{}, cc2_edge{};
     int ccf_tail = 0, ccf_kc2 = 0;       // k_ccf tail layers of shorter runs (ccf_layout)
+    bool ccf_edge_dot = false;           // ccgeo is the edge-sum form's tiling (one device, 60 x 29)
     std::vector<float> placement_ms;     // placement draws: ms per probe iteration, per draw
     int placement_pick = -1;             // the draw kept (-1: no draws)
     double* r2 = nullptr;                // k_ccf: r_{it+1} when r_it is in r (by parity)
@@ -183,6 +184,7 @@ struct hip_proj_ctx {
         bool rk_pair = true;      // CFD_HIP_RK_PAIR=0: per-cell RK4 stage
         bool alloc_contig = false;  // CFD_HIP_ALLOC=contig: contiguous field allocations
         bool ccf_edge_side = true;  // CFD_HIP_CCF_EDGE_SIDE=0: slab edge march before the interior
+        bool ccf_edge_dot = true;   // CFD_HIP_CCF_EDGE_DOT=0: one device keeps delta = (A r, r) cell by cell
     } env;
     // timing
     int timing = 0;

@@ -187,10 +187,22 @@ static void launch_ccf_t(hip_proj_ctx* c, const SGeo& g, const Lap& L, double* p
     // clock sample on one launch in eight while timing (iterations 5 and 7
     // mod 8: a plain and a fold launch)
     unsigned long long* clk = (c->timing && c->clk && (it & 5) == 5) ? c->clk : nullptr;
-    hipExtLaunchKernelGGL((k_ccf<FIRST, FOLD, NOC>), dim3(g.tiles_x * g.tiles_y * g.tiles_z),
-                          dim3(1024), 0, s, c->ta, c->tb, 0, g, L, ccf_r0(c, it),
-                          ccf_r1(c, it), po, pn, pv, x, c->st, c->partials, c->counter, it, xmap,
-                          dist(c) ? 1 : 0, c->dsum, mbox(c), clk);
+    // k_ccf<.., false> is the edge-sum form, whose 60 x 29 tiling only
+    // c->ccgeo of an edge-sum context has; every other march with stage c (a
+    // Z-slab's interior planes, CFD_HIP_CCF_EDGE_DOT=0) is k_ccf_cell
+    const bool cell = !NOC && !(c->ccf_edge_dot && g.kmode == 0);
+    const dim3 grid(g.tiles_x * g.tiles_y * g.tiles_z);
+    if (cell) {
+        if constexpr (!NOC)
+            hipExtLaunchKernelGGL((k_ccf_cell<FIRST, FOLD>), grid, dim3(1024), 0, s, c->ta, c->tb,
+                                  0, g, L, ccf_r0(c, it), ccf_r1(c, it), po, pn, pv, x, c->st,
+                                  c->partials, c->counter, it, xmap, dist(c) ? 1 : 0, c->dsum,
+                                  mbox(c), clk);
+        return;
+    }
+    hipExtLaunchKernelGGL((k_ccf<FIRST, FOLD, NOC>), grid, dim3(1024), 0, s, c->ta, c->tb, 0, g,
+                          L, ccf_r0(c, it), ccf_r1(c, it), po, pn, pv, x, c->st, c->partials,
+                          c->counter, it, xmap, dist(c) ? 1 : 0, c->dsum, mbox(c), clk);
 }
 
 template <bool NOC>
@@ -1278,6 +1290,7 @@ static cfd_status_t init_ctx(hip_proj_ctx* c, size_t nx, size_t ny, size_t nz) {
         c->env.rk_pair = ienv("CFD_HIP_RK_PAIR", 1) != 0;
         c->env.alloc_contig = getenv("CFD_HIP_ALLOC") && strcmp(getenv("CFD_HIP_ALLOC"), "contig") == 0;
         c->env.ccf_edge_side = ienv("CFD_HIP_CCF_EDGE_SIDE", 1) != 0;
+        c->env.ccf_edge_dot = ienv("CFD_HIP_CCF_EDGE_DOT", 1) != 0;
     }
     c->nx = nx;
     c->ny = ny;
@@ -1420,14 +1433,18 @@ static cfd_status_t init_ctx(hip_proj_ctx* c, size_t nx, size_t ny, size_t nz) {
             n_partials = std::max(n_partials, 2 * r2.tiles_x * r2.tiles_y * r2.tiles_z);
         }
         // the fused single-reduction CG iteration (k_ccf, ccf.hpp): 64 x 32
-        // cells loaded, 60 x 28 written; one device, 3-D
+        // cells loaded, 60 x 29 written on one device (delta as an edge sum),
+        // 60 x 28 on Z-slabs and with CFD_HIP_CCF_EDGE_DOT=0 (delta = (A r, r)
+        // cell by cell); 3-D
+        c->ccf_edge_dot = c->nranks == 1 && c->env.ccf_edge_dot;
+        const int ccf_oy = c->ccf_edge_dot ? CCF_OY_EDGE : CCF_OY;
         SGeo& cg = c->ccgeo;
         cg = rg;
         cg.tiles_x = cg.tiles_y = cg.tiles_z = 0;
         if (nz >= 3 && nx >= 4 && ny >= 4) {
             cg.xofs = 0;
             cg.tiles_x = (int)((nx - 1 + CCF_OX - 1) / CCF_OX);
-            cg.tiles_y = (int)((ny - 1 + CCF_OY - 1) / CCF_OY);
+            cg.tiles_y = (int)((ny - 1 + ccf_oy - 1) / ccf_oy);
             // z-run length: 24 planes on deep grids, 16 on thin ones (r05;
             // r04 had 32). 512^3 on one device: 24 at 1.048-1.049 vs 32's
             // 1.059 ms per iteration in every stable pair on two boxes (20 and
