@@ -243,6 +243,8 @@ def test_poisson_relax_bitwise(hip_lib, method):
     ((130, 20, 9), dict(max_iterations=40, check_interval=3)),  # two x tiles, odd ny
     ((17, 17, 17), dict(tolerance=1e-2)),                     # early stop, odd iterate
     ((250, 30, 40), dict(max_iterations=25)),                 # 3x3 one-pass tiles, z chunks
+    # dx != dy != dz (the 1.0 x 0.7 x 1.3 box): the x and y factors told apart
+    ((129, 17, 7), dict(max_iterations=12, box=(1.0, 0.7, 1.3))),
 ])
 def test_poisson_relax_fused_loop_bitwise(hip_lib, method, shape, kw):
     """The device loop (one-pass RB k_rb1 or the two colour sweeps of k_rx,
@@ -254,20 +256,23 @@ def test_poisson_relax_fused_loop_bitwise(hip_lib, method, shape, kw):
     rng = np.random.default_rng(nx * 7 + nz)
     rhs = rng.standard_normal((nz, ny, nx))
     x0 = 0.1 * rng.standard_normal((nz, ny, nx))
-    d = 1.0 / (nx - 1)
+    dx = dy = 1.0 / (nx - 1)
     dz = 1.0 / (nz - 1) if nz > 1 else 0.0
     base = dict(max_iterations=3000 if method == A.HIP_POISSON_JACOBI else 2000)
     base.update(kw)
+    box = base.pop("box", None)
+    if box:
+        dx, dy, dz = box[0] / (nx - 1), box[1] / (ny - 1), box[2] / (nz - 1)
     prm = oracle.poisson_params(**base)
     xo = x0.copy()
     if method == A.HIP_POISSON_REDBLACK:
-        so, sto = oracle.redblack_solve(xo, rhs, d, d, dz, prm)
+        so, sto = oracle.redblack_solve(xo, rhs, dx, dy, dz, prm)
     else:
-        so, sto = oracle.jacobi_solve(xo, rhs, d, d, dz, prm)
+        so, sto = oracle.jacobi_solve(xo, rhs, dx, dy, dz, prm)
     for two_pass in (0, 1, 2):  # one-pass RB (3-D) / host two-pass / device two-colour
         ctx = api.HipProjection(nx, ny, nz, relax_two_pass=two_pass)
         xh = x0.copy()
-        sh, sth = ctx.poisson_solve(method, xh, rhs, d, d, dz, prm)
+        sh, sth = ctx.poisson_solve(method, xh, rhs, dx, dy, dz, prm)
         ctx.close()
         assert sh == so, two_pass
         assert (sth.iterations, sth.status) == (sto.iterations, sto.status), two_pass

@@ -24,6 +24,13 @@ pytestmark = pytest.mark.gpu
     # nx = 124 T + 1: no remainder strip (the full tiles store every pair)
     ((249, 21, 10), dict(max_iterations=11)),
     ((250, 21, 10), dict(max_iterations=11)),
+    # the 1.0 x 0.7 x 1.3 box (dx != dy != dz: an exchange of the x and y
+    # factors is invisible on the cases above). A check_interval above 1
+    # routes every sweep past k_rb2 into k_rb1; 250 x 21 x 10 is the strip
+    # case, as above (k_rb1 for the first sweep only) and all k_rb1
+    ((130, 20, 9), dict(max_iterations=40, check_interval=3, box=(1.0, 0.7, 1.3))),
+    ((250, 21, 10), dict(max_iterations=11, box=(1.0, 0.7, 1.3))),
+    ((250, 21, 10), dict(max_iterations=11, check_interval=2, box=(1.0, 0.7, 1.3))),
 ])
 @pytest.mark.parametrize("tc", ["64", "32", "16"])
 def test_rb_one_pass_bitwise(hip_lib, shape, kw, tc, monkeypatch):
@@ -34,16 +41,19 @@ def test_rb_one_pass_bitwise(hip_lib, shape, kw, tc, monkeypatch):
     rng = np.random.default_rng(nx * 7 + nz)
     rhs = rng.standard_normal((nz, ny, nx))
     x0 = 0.1 * rng.standard_normal((nz, ny, nx))
-    d = 1.0 / (nx - 1)
+    dx = dy = 1.0 / (nx - 1)
     dz = 1.0 / (nz - 1)
     base = dict(max_iterations=2000)
     base.update(kw)
+    box = base.pop("box", None)
+    if box:
+        dx, dy, dz = box[0] / (nx - 1), box[1] / (ny - 1), box[2] / (nz - 1)
     prm = oracle.poisson_params(**base)
     xo = x0.copy()
-    so, sto = oracle.redblack_solve(xo, rhs, d, d, dz, prm)
+    so, sto = oracle.redblack_solve(xo, rhs, dx, dy, dz, prm)
     ctx = api.HipProjection(nx, ny, nz)
     xh = x0.copy()
-    sh, sth = ctx.poisson_solve(A.HIP_POISSON_REDBLACK, xh, rhs, d, d, dz, prm)
+    sh, sth = ctx.poisson_solve(A.HIP_POISSON_REDBLACK, xh, rhs, dx, dy, dz, prm)
     ctx.close()
     assert sh == so
     assert (sth.iterations, sth.status) == (sto.iterations, sto.status)
