@@ -10,6 +10,7 @@
 // is no host round trip per iteration (the reference GPU path does two per
 // iteration, poisson_cg_gpu_solve.cuh:189-203).
 #include "ctx.hpp"
+#include "../host/grid_spacing.h"
 
 #include <array>
 #include "rb2.hpp"
@@ -1149,6 +1150,17 @@ cfd_status_t ctx_validate_params(const hip_proj_ctx* c, const grid* g,
                     "projection_hip: host heat_source_func callbacks cannot run on the device");
             return CFD_ERROR_UNSUPPORTED;
         }
+        // energy_step_explicit_with_workspace (energy_solver.c:55-75) refuses
+        // non-uniform dx / dy after the reference's solvers have advanced the
+        // velocity; here the step is refused before any device work
+        if (g->dx && !grid_axis_is_uniform(g->dx, g->nx)) {
+            set_err(CFD_ERROR_UNSUPPORTED, "energy_solver: non-uniform dx not supported");
+            return CFD_ERROR_UNSUPPORTED;
+        }
+        if (g->dy && !grid_axis_is_uniform(g->dy, g->ny)) {
+            set_err(CFD_ERROR_UNSUPPORTED, "energy_solver: non-uniform dy not supported");
+            return CFD_ERROR_UNSUPPORTED;
+        }
         const ns_thermal_bc_config_t& t = prm->thermal_bc;
         auto ok = [](bc_type_t b) {
             return b == BC_TYPE_PERIODIC || b == BC_TYPE_NEUMANN || b == BC_TYPE_DIRICHLET;
@@ -1655,7 +1667,9 @@ static cfd_status_t init_ctx(hip_proj_ctx* c, size_t nx, size_t ny, size_t nz) {
     }
     if (dalloc(c, &c->src_u_row, ny) != CFD_SUCCESS) return CFD_ERROR;
     if (dalloc(c, &c->src_v_col, nx) != CFD_SUCCESS) return CFD_ERROR;
-    HIP_TRY(hipHostMalloc((void**)&c->h_src, (nx + ny) * sizeof(double), hipHostMallocDefault));
+    // source tables (ny + nx), then the integrators' staged dx[nx], dy[ny]
+    HIP_TRY(hipHostMalloc((void**)&c->h_src, 2 * (nx + ny) * sizeof(double),
+                          hipHostMallocDefault));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_src, hipEventDisableTiming));
     HIP_TRY(hipMalloc((void**)&c->st, sizeof(CgState)));
     HIP_TRY(hipMemsetAsync(c->st, 0, sizeof(CgState), c->stream));

@@ -13,6 +13,7 @@
 // between the context's CG work arrays (u*,v*,w*,p_new and r,p_a,p_b,x_tmp);
 // the final update is written in place over u,v,w,p.
 #include "ctx.hpp"
+#include "../host/grid_spacing.h"
 
 // stages: the running k sums and x_tmp (RK4 / RK2); explicit Euler needs neither
 static cfd_status_t ensure_rk(hip_proj_ctx* c, bool stages) {
@@ -99,8 +100,15 @@ static cfd_status_t step_head(hip_proj_ctx* c, const grid* g, const ns_solver_pa
 
     // per-index spacing and compute_source_terms tables (iter-dependent decay),
     // evaluated on the host with the reference's libm expressions
-    HIP_TRY(hipMemcpyAsync(c->dxa, g->dx, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->dya, g->dy, ny * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // (the grid holds nx - 1 and ny - 1 spacings: grid_spacing.h fills the
+    // last slot; the pinned staging is h_src's second half, which ev_src
+    // guards together with the source tables)
+    HIP_TRY(hipEventSynchronize(c->ev_src));
+    double* hdx = c->h_src + nx + ny;
+    double* hdy = hdx + nx;
+    grid_stage_spacing(g, hdx, hdy);
+    HIP_TRY(hipMemcpyAsync(c->dxa, hdx, nx * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->dya, hdy, ny * sizeof(double), hipMemcpyHostToDevice, c->stream));
     ns_solver_params_t ps = *prm;
     ps.dt = src_dt;
     ST_TRY(upload_source_tables(c, g, &ps, iter));

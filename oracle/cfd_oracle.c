@@ -674,6 +674,18 @@ cfd_status_t oracle_energy_step(flow_field* field, const grid* g, const ns_solve
     size_t plane = nx * ny, total = plane * nz;
     double alpha = params->alpha;
     double dx0 = g->dx[0], dy0 = g->dy[0];
+    /* the stencil assumes uniform spacing (energy_solver.c:55-91) */
+    double tol_x = 1e-12 * fmax(1.0, fabs(dx0)), tol_y = 1e-12 * fmax(1.0, fabs(dy0));
+    for (size_t i = 1; i < nx - 1; i++)
+        if (fabs(g->dx[i] - dx0) > tol_x) return CFD_ERROR_UNSUPPORTED;
+    for (size_t j = 1; j < ny - 1; j++)
+        if (fabs(g->dy[j] - dy0) > tol_y) return CFD_ERROR_UNSUPPORTED;
+    if (nz > 1) {
+        if (!g->dz) return CFD_ERROR_INVALID;
+        double dz0 = g->dz[0], tol_z = 1e-12 * fmax(1.0, fabs(dz0));
+        for (size_t k = 1; k < nz - 1; k++)
+            if (fabs(g->dz[k] - dz0) > tol_z) return CFD_ERROR_UNSUPPORTED;
+    }
     double inv_2dx = 1.0 / (2.0 * dx0);
     double inv_2dy = 1.0 / (2.0 * dy0);
     double inv_dx2 = 1.0 / (dx0 * dx0);

@@ -5,8 +5,11 @@ solvers (the oracle restates neither integrator):
   tests/golden/euler_rk2_cases.json     per case and integrator: sha256 of the
                                         inputs, sha256 + sum / L2 / max of every
                                         output field, shape, flags, dt, steps,
-                                        call pattern
+                                        call pattern; for stretched grids sha256 of
+                                        x, y, dx, dy; `refusals`: the status of
+                                        each solver on two inputs it refuses
   tests/golden/euler_rk2_17x13x11.npz   full output fields of case "s17"
+  tests/golden/euler_rk2_st17x13x11.npz full output fields of case "st17"
 
 The reference checkout (CFD_REFERENCE_DIR, else `reference` beside this
 repository) is copied to a work directory and built there unmodified with its
@@ -101,6 +104,8 @@ def main():
         rec = {"shape": list(case["shape"]), "buoy": case["buoy"], "energy": case["energy"],
                "seed": case["seed"], "inputs": {k: R.sha(getattr(f0, k)) for k in R.FIELDS},
                "runs": {}}
+        if case["stretch"]:
+            rec["grid"] = {k: R.sha(v) for k, v in R.grid_arrays(g).items()}
         for integ in R.INTEGRATORS:
             f = api.FlowField(*case["shape"])
             f.copy_from(f0)
@@ -135,12 +140,21 @@ def main():
                 run_rec["guard"] = {"u_increments_clamped_step1": clamped,
                                     "rho0_interior_cells_kept": kept}
             rec["runs"][integ] = run_rec
-            if case["name"] == R.NPZ_CASE and integ != "rk4":
+            if case["name"] in R.NPZ_FILES and integ != "rk4":
                 for k in R.FIELDS:
-                    npz[f"{integ}_{k}"] = getattr(f, k).copy()
+                    npz.setdefault(case["name"], {})[f"{integ}_{k}"] = getattr(f, k).copy()
         doc["cases"][case["name"]] = rec
+    # inputs the reference refuses: the status of each solver, one call
+    doc["refusals"] = {}
+    for which in R.REFUSALS:
+        doc["refusals"][which] = {}
+        for integ in R.INTEGRATORS:
+            g, f, p = R.refusal_inputs(which)
+            doc["refusals"][which][integ] = int(getattr(ref, IMPL[integ])(f.ptr, g.ptr,
+                                                                          C.byref(p)))
     (OUT / "euler_rk2_cases.json").write_text(json.dumps(doc, indent=1) + "\n")
-    np.savez_compressed(OUT / "euler_rk2_17x13x11.npz", **npz)
+    for name, arrays in npz.items():
+        np.savez_compressed(OUT / R.NPZ_FILES[name], **arrays)
     print(json.dumps({"cases": len(doc["cases"]), "work": str(work)}))
 
 

@@ -40,8 +40,8 @@ def _check_fields(name, integ, f):
     for k in R.FIELDS:
         got = R.digest(getattr(f, k))
         assert got["sha256"] == want[k]["sha256"], (name, integ, k, got, want[k])
-    if name == R.NPZ_CASE:
-        z = np.load(GOLDEN / "euler_rk2_17x13x11.npz")
+    if name in R.NPZ_FILES:
+        z = np.load(GOLDEN / R.NPZ_FILES[name])
         for k in R.FIELDS:
             np.testing.assert_array_equal(getattr(f, k), z[f"{integ}_{k}"], err_msg=k)
 
@@ -85,7 +85,16 @@ def test_solve_method_gpu_bitwise(hip_lib, name, integ):
 
 @pytest.mark.parametrize("integ", NEW)
 def test_device_resident_matches_host_path(hip_lib, integ):
-    case = R.BY_NAME["s17_be"]
+    _device_resident_matches_host_path(integ, "s17_be")
+
+
+@pytest.mark.parametrize("integ", NEW)
+def test_device_resident_matches_host_path_stretched(hip_lib, integ):
+    _device_resident_matches_host_path(integ, "st17_b")
+
+
+def _device_resident_matches_host_path(integ, name):
+    case = R.BY_NAME[name]
     g, f, p = R.make_inputs(case)
     n = R.params_for(case, integ, p)
     ctx = api.HipProjection(*case["shape"])
@@ -101,7 +110,7 @@ def test_device_resident_matches_host_path(hip_lib, integ):
     ctx2.close()
     for k in IDS:
         np.testing.assert_array_equal(dev[k], getattr(f, k), err_msg=k)
-    _check_fields("s17_be", integ, f)
+    _check_fields(name, integ, f)
 
 
 @pytest.mark.parametrize("integ", NEW)

@@ -2,8 +2,10 @@
 AddressSanitizer + UndefinedBehaviorSanitizer into a C driver that walks the
 host API: grids and fields, every BC, the registry without a HIP library,
 restart-file round trip and corrupt-file rejection, VTK writers, the Poisson
-factory surface, and oracle projection / CG / RB-SOR / RK4 steps. Sanitizers
-run on host code only (there is no GPU sanitizer on this pool)."""
+factory surface, the integrators' staging of the per-index spacing
+(grid_spacing.h, on a created grid and on one read from a restart file), and
+oracle projection / CG / RB-SOR / RK4 steps. Sanitizers run on host code only
+(there is no GPU sanitizer on this pool)."""
 import os
 import shutil
 import subprocess
@@ -21,8 +23,26 @@ DRIVER = r"""
 #include <string.h>
 #include "cfd_hip/cfd_host.h"
 #include "oracle.h"
+#include "grid_spacing.h"
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
+
+/* the integrators' staging of dx[nx - 1], dy[ny - 1] into nx and ny device
+ * slots (rk4_hip.hip step_head), into heap blocks of exactly that size */
+static int check_staging(const grid* g) {
+    size_t nx = g->nx, ny = g->ny;
+    double* sx = (double*)malloc(nx * sizeof(double));
+    double* sy = (double*)malloc(ny * sizeof(double));
+    CHECK(sx && sy);
+    grid_stage_spacing(g, sx, sy);
+    for (size_t i = 0; i + 1 < nx; i++) CHECK(sx[i] == g->dx[i]);
+    for (size_t j = 0; j + 1 < ny; j++) CHECK(sy[j] == g->dy[j]);
+    CHECK(sx[nx - 1] == g->dx[nx - 2] && sy[ny - 1] == g->dy[ny - 2]);
+    CHECK(grid_axis_is_uniform(g->dx, nx) && grid_axis_is_uniform(g->dy, ny));
+    free(sx);
+    free(sy);
+    return 0;
+}
 
 int main(int argc, char** argv) {
     const char* dir = argv[1];
@@ -31,6 +51,13 @@ int main(int argc, char** argv) {
     grid* g = grid_create(nx, ny, nz, 0, 1, 0, 1, 0, 1);
     CHECK(g);
     grid_initialize_uniform(g);
+    CHECK(check_staging(g) == 0);
+    double keep = g->dx[nx - 2]; /* the last entry the energy equation's check reads */
+    g->dx[nx - 2] = keep + 2e-12;
+    CHECK(!grid_axis_is_uniform(g->dx, nx));
+    g->dx[nx - 2] = keep + 5e-13;
+    CHECK(grid_axis_is_uniform(g->dx, nx));
+    g->dx[nx - 2] = keep;
     flow_field* f = flow_field_create(nx, ny, nz);
     CHECK(f);
     initialize_flow_field(f, g);
@@ -60,6 +87,7 @@ int main(int argc, char** argv) {
     CHECK(cfd_checkpoint_read(path, &g2, &f2, &p2, &t2, name, sizeof name, pre, sizeof pre,
                               base, sizeof base) == CFD_SUCCESS);
     CHECK(t2 == 1.5 && memcmp(f2->u, f->u, nx * ny * nz * sizeof(double)) == 0);
+    CHECK(check_staging(g2) == 0); /* the reader's grid has nx - 1 / ny - 1 spacings too */
     flow_field_destroy(f2);
     grid_destroy(g2);
     FILE* fp = fopen(path, "r+b");

@@ -32,7 +32,13 @@ def test_case_table_matches_fixture():
             assert run["dt"] == R.case_dt(case, integ)
             assert run["steps"] == R.case_steps(case, integ)
             assert run["pattern"] == ("steps" if integ == "rk4" else case["pattern"])
+        assert ("grid" in rec) == case["stretch"]
+        assert not (case["stretch"] and case["energy"])  # the reference refuses that pair
     assert any(c["dt"] > 1e-4 for c in R.CASES)  # explicit Euler's 1e-4 cap acts
+    assert any(c["dt"] > 1e-4 and c["stretch"] for c in R.CASES)
+    assert sorted(DOC["refusals"]) == sorted(R.REFUSALS)
+    for rec in DOC["refusals"].values():
+        assert sorted(rec) == sorted(R.INTEGRATORS)
     g = DOC["cases"]["guard17"]["runs"]["euler"]["guard"]
     assert g["u_increments_clamped_step1"] > 0 and g["rho0_interior_cells_kept"] > 0
 
@@ -40,9 +46,12 @@ def test_case_table_matches_fixture():
 @pytest.mark.parametrize("name", NAMES)
 def test_inputs_regenerate(name):
     """A drifted generator reads as an input mismatch, not as a kernel failure."""
-    _, f, _ = R.make_inputs(R.BY_NAME[name])
+    g, f, _ = R.make_inputs(R.BY_NAME[name])
     for k in R.FIELDS:
         assert R.sha(getattr(f, k)) == DOC["cases"][name]["inputs"][k], f"input {k}"
+    if R.BY_NAME[name]["stretch"]:
+        for k, v in R.grid_arrays(g).items():
+            assert R.sha(v) == DOC["cases"][name]["grid"][k], f"grid {k}"
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -58,11 +67,151 @@ def test_oracle_reproduces_reference_rk4(name):
 
 
 def test_npz_matches_digests():
-    z = np.load(GOLDEN / "euler_rk2_17x13x11.npz")
-    for integ in ("euler", "rk2"):
-        want = DOC["cases"][R.NPZ_CASE]["runs"][integ]["outputs"]
-        for k in R.FIELDS:
-            assert R.digest(z[f"{integ}_{k}"]) == want[k], (integ, k)
+    for name, file in R.NPZ_FILES.items():
+        z = np.load(GOLDEN / file)
+        for integ in ("euler", "rk2"):
+            want = DOC["cases"][name]["runs"][integ]["outputs"]
+            for k in R.FIELDS:
+                assert R.digest(z[f"{integ}_{k}"]) == want[k], (name, integ, k)
+
+
+# --- stretched grids: the inputs vary enough, and the fixtures tell a wrong
+# --- spacing index from the right one
+STRETCHED = [c["name"] for c in R.CASES if c["stretch"] and not c["zero"]]
+STRETCHED_STEPS = [n for n in STRETCHED if R.BY_NAME[n]["pattern"] == "steps"]
+
+
+def _interior(a):
+    return a[1:-1, 1:-1, 1:-1] if a.shape[0] > 1 else a[:, 1:-1, 1:-1]
+
+
+@pytest.mark.parametrize("name", STRETCHED)
+def test_stretched_spacing_varies(name):
+    case = R.BY_NAME[name]
+    g, f, _ = R.make_inputs(case)
+    ga = R.grid_arrays(g)
+    nx, ny, _ = case["shape"]
+    assert len(ga["dx"]) == nx - 1 and len(ga["dy"]) == ny - 1
+    assert np.all(ga["dx"] > 0.0) and np.all(ga["dy"] > 0.0)
+    if ny > 3:
+        assert ga["dx"].max() / ga["dx"].min() >= 3.0
+        assert ga["dy"].max() / ga["dy"].min() >= 2.5
+    for d in (ga["dx"], ga["dy"]):
+        # the map is symmetric about the middle: with an even number of
+        # spacings the centre pair is equal, and only that pair
+        eq = np.flatnonzero(d[1:] == d[:-1])
+        centre = [len(d) // 2 - 1] if len(d) % 2 == 0 else []
+        assert [e for e in eq if e not in centre] == [], (name, eq)
+    # second differences of u as the RHS forms them (periodic neighbours over
+    # the interior, / dx[i]^2 and / dy[j]^2): the +-1000 clamp stays rare
+    u = f.u
+
+    def nb(a, axis, step):  # interior neighbour with the RHS's wrap 1 <-> n - 2
+        n = a.shape[axis]
+        idx = np.arange(1, n - 1) + step
+        idx = np.where(idx < 1, n - 2, np.where(idx > n - 2, 1, idx))
+        return np.take(a, idx, axis=axis)
+
+    uc = _interior(u)
+    ks = slice(1, -1) if u.shape[0] > 1 else slice(None)
+    ux = u[ks, 1:-1, :]
+    uy = u[ks, :, 1:-1]
+    d2x = (nb(ux, 2, 1) - 2.0 * uc + nb(ux, 2, -1)) / (ga["dx"][1:nx - 1] ** 2)[None, None, :]
+    d2y = (nb(uy, 1, 1) - 2.0 * uc + nb(uy, 1, -1)) / (ga["dy"][1:ny - 1] ** 2)[None, :, None]
+    clamped = (np.abs(d2x) > 1000.0) | (np.abs(d2y) > 1000.0)
+    assert clamped.mean() <= 0.01, (name, float(clamped.mean()))
+
+
+def _write_spacing(g, dx, dy):
+    for i, v in enumerate(dx):
+        g.c.dx[i] = v
+    for j, v in enumerate(dy):
+        g.c.dy[j] = v
+
+
+def _swap_pairs(d):
+    out = d.copy()
+    for i0 in range(0, len(d) - 1, 2):
+        out[i0], out[i0 + 1] = d[i0 + 1], d[i0]
+    return out
+
+
+@pytest.mark.parametrize("name", STRETCHED_STEPS)
+def test_stretched_fixture_discriminates(name):
+    """One oracle RK4 step on the true grid and on grids whose spacing arrays
+    carry a fault a kernel could have: each changes u, v and p in at least
+    99 % of the interior cells, so a bitwise comparison cannot miss it."""
+    case = R.BY_NAME[name]
+
+    def step(mutate):
+        g, f, p = R.make_inputs(case)
+        R.params_for(case, "rk4", p, "steps")
+        ga = R.grid_arrays(g)
+        if mutate:
+            _write_spacing(g, *mutate(ga["dx"], ga["dy"]))
+        s, _ = oracle.rk4_step(f, g, p)
+        assert s == A.CFD_SUCCESS
+        return f
+
+    true = step(None)
+    mutations = {
+        "dx swapped in pairs": lambda dx, dy: (_swap_pairs(dx), dy),
+        "dx rolled": lambda dx, dy: (np.roll(dx, 1), dy),
+        "dx[0], dy[0] everywhere": lambda dx, dy: (np.full_like(dx, dx[0]),
+                                                   np.full_like(dy, dy[0])),
+    }
+    if case["shape"][1] > 3:  # ny = 3: both dy entries are equal
+        mutations["dy rolled"] = lambda dx, dy: (dx, np.roll(dy, 1))
+    for what, m in mutations.items():
+        got = step(m)
+        for k in ("u", "v", "p"):
+            share = float(np.mean(_interior(getattr(got, k)) != _interior(getattr(true, k))))
+            assert share >= 0.99, (name, what, k, share)
+
+
+def test_zero_spacing_guard_case():
+    """stzero17: the interior cells of columns 5, 10 (|dx[i]| < 1e-10) and of
+    row 3 (dy[3] = 0) keep their values through an RK4 step; column 4 moves."""
+    case = R.BY_NAME["stzero17"]
+    g, f, p = R.make_inputs(case)
+    ga = R.grid_arrays(g)
+    assert ga["dx"][5] == 0.0 and 0.0 < ga["dx"][10] < 1e-10 and ga["dy"][3] == 0.0
+    assert sum(abs(d) < 1e-10 for d in ga["dx"]) == 2 and sum(abs(d) < 1e-10 for d in ga["dy"]) == 1
+    before = f.arrays()
+    R.params_for(case, "rk4", p, "steps")
+    s, _ = oracle.rk4_step(f, g, p)
+    assert s == A.CFD_SUCCESS
+    for k in ("u", "v", "w", "p"):
+        a, b = getattr(f, k), before[k]
+        assert np.all(np.isfinite(a))
+        for i in R.ZERO_COLS:
+            np.testing.assert_array_equal(a[1:-1, 1:-1, i], b[1:-1, 1:-1, i], err_msg=f"{k} col {i}")
+        for j in R.ZERO_ROWS:
+            np.testing.assert_array_equal(a[1:-1, j, 1:-1], b[1:-1, j, 1:-1], err_msg=f"{k} row {j}")
+    keep = [j for j in range(1, 12) if j not in R.ZERO_ROWS]
+    for k in ("u", "v", "p"):
+        assert np.all(getattr(f, k)[1:-1, keep, 4] != before[k][1:-1, keep, 4]), k
+
+
+def test_oracle_refuses_what_the_reference_refuses():
+    """Energy equation on a stretched x / y grid: energy_step_explicit's
+    uniformity check, which the projection and RK4 solvers propagate;
+    non-uniform dz: the solvers' own check."""
+    want = DOC["refusals"]["stretched_xy_with_energy"]
+    assert want["rk4"] == A.CFD_ERROR_UNSUPPORTED  # what the record holds today
+    g, f, p = R.refusal_inputs("stretched_xy_with_energy")
+    assert oracle.rk4_step(f, g, p)[0] == want["rk4"]
+    g, f, p = R.refusal_inputs("stretched_xy_with_energy")
+    assert oracle.projection_step(f, g, p)[0] == want["rk4"]
+    assert oracle.lib().oracle_energy_step(f.ptr, g.ptr, api.C.byref(p), 1e-4,
+                                           0.0) == want["rk4"]
+    # uniform grids pass the same check
+    g, f, p = R.make_inputs(R.BY_NAME["s17_be"])
+    assert oracle.lib().oracle_energy_step(f.ptr, g.ptr, api.C.byref(p), 1e-4,
+                                           0.0) == A.CFD_SUCCESS
+    want = DOC["refusals"]["nonuniform_dz"]
+    g, f, p = R.refusal_inputs("nonuniform_dz")
+    assert oracle.rk4_step(f, g, p)[0] == want["rk4"] == A.CFD_ERROR_INVALID
 
 
 def test_new_entry_points_are_exported():
