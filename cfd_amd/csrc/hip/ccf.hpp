@@ -90,9 +90,7 @@ constexpr int CCF_LDAUX = CFD_CCF_LDAUX;
 constexpr bool CCF_NTFOLD = CFD_CCF_NTFOLD != 0;
 constexpr int CCF_TC = 32;  // x pairs per tile row
 constexpr int CCF_TR = 32;  // tile rows
-constexpr int CCF_OX = 60;  // columns written per tile
-constexpr int CCF_OY = 28;  // rows written per tile
-constexpr int CCF_OY_EDGE = 29;  // ... in the edge-sum form (ccf_body EDGE)
+// CCF_OX x CCF_OY (CCF_OY_EDGE in the edge-sum form) cells written: tile_plan.hpp
 // LDS plane: rows of 2 padded halves (.x cells, then .y cells) so that an x
 // neighbour (one double of the adjacent lane) is a conflict-free 8-B read
 constexpr int CCF_LP = CCF_TC + 2;

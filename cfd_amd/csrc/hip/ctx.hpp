@@ -52,33 +52,12 @@ struct TimedLaunch {
 
 }  // namespace
 
-struct hip_proj_ctx {
+// The launch geometry (px, ps, geo, the SGeos, the split and variant flags,
+// stagger_bytes, n_partials) is the TilePlan base, planned once in init_ctx.
+struct hip_proj_ctx : TilePlan {
     int device = 0;
     hipStream_t stream = nullptr;
     size_t nx = 0, ny = 0, nz = 0;
-    long long px = 0, ps = 0;
-    Geo geo{};
-    SGeo sgeo{};       // row-pair CG sweep tiling
-    SGeo sg_edge{}, sg_int{};  // slabs: sweep B split into edge planes + interior
-    SGeo rgeo{};               // single-pass RB-SOR tiling (k_rb1)
-    // slabs: one k_rb1 iteration as three launches sharing one reduction --
-    // interior part 1 (overlaps the R halo exchange), the two edge planes,
-    // interior part 2 (overlaps the exchange of the new iterate's edge planes)
-    SGeo rg_in1{}, rg_edge{}, rg_in2{};
-    int split_rb = 0;
-    // one device: k_rb1's full-width (TC 64) tiles stop at x = 124 T, and the
-    // remaining columns run as a strip of narrow tiles (TC 16 / 32) in a
-    // second launch sharing the residual reduction (rb_strip_tc 0: none)
-    SGeo rg_main{}, rg_strip{};
-    int rb_strip_tc = 0;
-    int rb1_tc = 64;           // k_rb1 tile width in x pairs (64, 32, 16)
-    SGeo pgeo{};               // predictor / corrector z-march tiling (k_pred2, k_corr2)
-    SGeo pgeo16{};             // k_pred3 / k_corr3: 128 x 16 tiles, y rows in LDS
-    int pc3 = 1;  // 0: k_pred2 / k_corr2; k_pred3 / k_corr3 with 1: FL 0 (default), 2: NT stores, 4: + NT loads
-    int split_b = 0;
-    int sweep_ty = 8;  // waves (y rows) per CG sweep workgroup
-    int sweep_variant = 0;  // SW_NT_* flags of the CG sweeps
-    int sweep_variant_fold = 0;  // the fold sweep's flags (0: sweep_variant)
     int grid_cap = 2048;
     hip_proj_config_t cfg{};
     // Z-slab decomposition (nranks == 1: the whole grid, no communicator)
@@ -138,14 +117,6 @@ struct hip_proj_ctx {
     RxState* rxst = nullptr;             // fused relaxation loop state
     RxState* rxst2 = nullptr;            // scratch state of k_rb2's recompute sweeps
     void* rb2dec = nullptr;              // k_rb2's decision constants (Rb2Dec, rb2.hpp)
-    SGeo r2geo{};                        // two-iterations-per-sweep RB-SOR tiling (k_rb2)
-    SGeo ccgeo{};                        // fused single-reduction CG tiling (k_ccf)
-    SGeo cc_edge{}, cc_int{};            // slabs: k_ccf on the edge planes, then the rest
-    // slabs, fused form: cc_int with stage c and a shared reduction, and
-    // k_cc2's tiling of the two edge planes completing it (tiles_x 0: off)
-    SGeo cc_int_red{}, cc2_edge{};
-    int ccf_tail = 0, ccf_kc2 = 0;       // k_ccf tail layers of shorter runs (ccf_layout)
-    bool ccf_edge_dot = false;           // ccgeo is the edge-sum form's tiling (one device, 60 x 29)
     std::vector<float> placement_ms;     // placement draws: ms per probe iteration, per draw
     int placement_pick = -1;             // the draw kept (-1: no draws)
     double* r2 = nullptr;                // k_ccf: r_{it+1} when r_it is in r (by parity)
@@ -162,30 +133,7 @@ struct hip_proj_ctx {
     poisson_solver_stats_t pstats{};
     size_t bytes = 0;
     std::vector<void*> allocs;  // hipMalloc bases of the field arrays
-    size_t stagger_bytes = 0;
-    // Environment switches of the solve paths, read ONCE when the context
-    // is created (init_ctx), never per step or per solve: rank threads of an
-    // in-process group would otherwise call getenv while another thread of
-    // the process (a test fixture, the runtime) may change the environment,
-    // and getenv is not safe against a concurrent setenv / putenv. Tests set
-    // the variables before they create contexts.
-    struct {
-        bool ccf_off = false;     // CFD_HIP_CCF=0: k_cc1 + k_cc2 instead of k_ccf
-        int cg_small = -1;        // CFD_HIP_CG_SMALL (-1 unset, 0 never, 1 up to 1M cells)
-        int rb2_test = 0;         // CFD_HIP_RB2_TEST: force k_rb2's host paths
-        int rb2_xmap = 0;         // CFD_HIP_RB2_XMAP (experiments)
-        bool rb2_log = false;     // CFD_HIP_RB2_LOG (diagnostics)
-        int rb2 = 1;              // CFD_HIP_RB2: 1 certified fast, 2 exact, 0 k_rb1
-        int ccf_xmap = 0;         // CFD_HIP_CCF_XMAP: k_ccf tile order (experiments)
-        bool cgb_rev = true;      // CFD_HIP_CGB_REV=0: sweep B marches upwards
-        bool rb1_pf = true;       // CFD_HIP_RB1_PF=0: k_rb1 end-of-step loads
-        bool rb1_alt = true;      // CFD_HIP_RB1_ALT=0: every k_rb1 sweep upwards
-        bool rb1_fold = true;     // CFD_HIP_RB1_FOLD=0: separate k_rx_shell launch
-        bool rk_pair = true;      // CFD_HIP_RK_PAIR=0: per-cell RK4 stage
-        bool alloc_contig = false;  // CFD_HIP_ALLOC=contig: contiguous field allocations
-        bool ccf_edge_side = true;  // CFD_HIP_CCF_EDGE_SIDE=0: slab edge march before the interior
-        bool ccf_edge_dot = true;   // CFD_HIP_CCF_EDGE_DOT=0: one device keeps delta = (A r, r) cell by cell
-    } env;
+    Knobs env;  // the CFD_HIP_* switches, read once at creation (tile_plan.hpp)
     // timing
     int timing = 0;
     std::vector<hipEvent_t> ev_pool;

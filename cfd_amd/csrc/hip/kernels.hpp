@@ -31,11 +31,11 @@
 #include <type_traits>
 
 #include "mbox.hpp"
+#include "tile_plan.hpp"
 
 namespace cfdhip {
 
-constexpr int TX = 64;       // x extent of a tile = one wavefront
-constexpr int TY = 4;        // y rows per tile
+// TX x TY: the tile of the grid-stride kernels (tile_plan.hpp)
 constexpr int NT = TX * TY;  // threads per workgroup
 constexpr int NWAVE = NT / 64;
 
@@ -43,18 +43,6 @@ constexpr int NWAVE = NT / 64;
 constexpr int ST_CONVERGED = 0;
 constexpr int ST_MAX_ITER = 1;
 constexpr int ST_STAGNATED = 3;
-
-struct Geo {
-    int nx, ny, nz;        // points of the local array, boundary included
-    long long px;          // row pitch (doubles)
-    long long ps;          // plane pitch (doubles)
-    long long sz;          // z stencil offset: ps in 3-D, 0 in 2-D (reference stride_z)
-    int k0, k1;            // interior planes [k0, k1)
-    int kc;                // planes per tile
-    int tiles_x, tiles_y, tiles_z;
-    int lo_face, hi_face;  // local plane 0 / nz-1 is a global z face (Z-slabs: edge ranks)
-    int kofs;              // global index of local plane 0 (Z-slabs)
-};
 
 struct Lap {
     double dx2_inv, dy2_inv, inv_dz2;  // linear_solver_cg.c:103-110
@@ -391,32 +379,7 @@ static __global__ __launch_bounds__(NT) void k_cg_setup(Geo g, Lap L, DivCoef dc
 // Measured at 512^3 (tools/mb/stencil_mb6.hip): 5.2 TB/s for sweep A versus
 // 4.3-4.5 TB/s for one-cell-per-lane designs.
 // ===========================================================================
-struct SGeo {
-    int nx, ny, nz;
-    long long px, ps, sz;
-    int k0, k1, kc;
-    int tiles_x, tiles_y, tiles_z;  // tiles of 128 x TY x kc
-    // kmode 1: the two slab-edge planes only (tz 0 -> plane k0, tz 1 -> k1-1),
-    // one plane per tile; the launch covering the remaining planes uses
-    // k0+1 .. k1-1. A sweep split over several launches shares one partials
-    // array: this launch's workgroups own partials [part_ofs, part_ofs +
-    // gridDim.x) of part_total, and the last of all part_total workgroups
-    // (same stream, so the later launch) finishes the reduction.
-    int kmode;
-    int part_ofs, part_total;
-    int kofs;  // global index of local plane 0 (Z-slabs; colour parity)
-    // kmode 2 (k_rb1 on slabs): tiles cover planes [kt0, kt1) only, while
-    // k0 / k1 still bound the planes that are updated
-    int kt0, kt1;
-    // k_rb1: x of the first tile's first output column (the narrow
-    // remainder strip starts where the full-width tiles end)
-    int xofs;
-    // k_ccf (kmode 0 / 2): z layers tz < nz1 run kc planes from the range's
-    // start; layers tz >= nz1 ("tail") run kc2 planes from plane start +
-    // nz1 kc, so the last-dispatched workgroups are short (nz1 = tiles_z:
-    // every layer kc planes)
-    int kc2, nz1;
-};
+// SGeo, the tiling of one launch: tile_plan.hpp
 
 __device__ __forceinline__ int xcd_tile(int b, int nt) {
     // bijective remap: block b runs on XCD b % 8 (round-robin dispatch);
@@ -434,10 +397,7 @@ __device__ __forceinline__ void st2(double* p, long long i, double2 v) {
     *reinterpret_cast<double2*>(p + i) = v;
 }
 
-// Sweep variants (template FL): bit 0 = non-temporal stores of the streamed
-// outputs, bit 1 = non-temporal loads of inputs no other tile reads.
-constexpr int SW_NT_STORE = 1;
-constexpr int SW_NT_LOAD = 2;
+// Sweep variants (template FL): the SW_* flags of tile_plan.hpp.
 typedef double d2x __attribute__((ext_vector_type(2)));
 template <int FL>
 __device__ __forceinline__ void st2v(double* p, long long i, double2 v) {
@@ -538,18 +498,6 @@ __device__ __forceinline__ RowPair row_pair(const SGeo& g) {
     return c;
 }
 
-// Loads of one plane step are issued through a small "bundle": without
-// SW_PREFETCH the bundle of plane k is loaded at the top of iteration k (and
-// its centre loads are consumed in the same iteration); with SW_PREFETCH the
-// bundle of plane k+1 is issued before plane k is processed, so one plane of
-// loads stays in flight across the LDS barrier and the arithmetic.
-constexpr int SW_PREFETCH = 4;
-// bit 3: the two x-edge cells of a row (lane 0's left, lane 63's right
-// neighbour) are fetched by ONE load instruction with per-lane addresses;
-// bit 4: the centre rows of the inner waves of a stencil field (rows no
-// neighbouring tile re-reads as its y halo) are loaded non-temporally.
-constexpr int SW_EDGE1 = 8;
-constexpr int SW_NT_INNER = 16;
 // (r01e: asking for 8 waves per SIMD, i.e. <= 64 VGPRs and two 1024-thread
 // workgroups per CU, spills and is slower; profiles/r01e_sweep_variants.jsonl)
 template <int FL>
@@ -900,7 +848,6 @@ static __global__ __launch_bounds__(64 * TY, sweep_min_waves<FL>()) void k_cgB(
 // ST_COMM_TIMEOUT instead of hanging the GPU).
 // ---------------------------------------------------------------------------
 constexpr int CGS_THREADS = 256;
-constexpr int CGS_MAX_WG = 256;
 constexpr long long CG_SMALL_CELLS = 300000;  // default ceiling (interior cells): 64^3 yes, 96^3 no
 
 static __global__ __launch_bounds__(CGS_THREADS) void k_cg_small(Geo g, Lap L,
@@ -2903,10 +2850,7 @@ static __global__ __launch_bounds__(256) void k_rb_edge_r(SGeo g, RelaxCoef rc,
 #ifndef CFD_PR_SYNC
 #define CFD_PR_SYNC 1
 #endif
-#ifndef CFD_PR_TY
-#define CFD_PR_TY 4
-#endif
-constexpr int PR_TY = CFD_PR_TY;  // rows (waves) per workgroup
+// PR_TY rows (waves) per workgroup (tile_plan.hpp, -DCFD_PR_TY)
 
 // a / d correctly rounded, like divc, for operands that are often exactly
 // zero (derivatives of a field at rest): e = q d - a and q - e r give the
@@ -3296,7 +3240,7 @@ static __global__ __launch_bounds__(64 * PR_TY, PF ? 3 : 4) void k_corr2(
 // theirs. FL: SW_NT_STORE = non-temporal stores of the outputs, SW_NT_LOAD =
 // non-temporal loads of the pointwise inputs (the corrector's u*, v*, w*).
 // ---------------------------------------------------------------------------
-constexpr int PC_TY = 16;
+// PC_TY = 16 rows per workgroup (tile_plan.hpp)
 
 template <bool BUOY, int FL>
 static __global__ __launch_bounds__(64 * PC_TY, 1) void k_pred3(

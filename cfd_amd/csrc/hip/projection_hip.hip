@@ -792,15 +792,10 @@ static cfd_status_t relax_solve_rb2(hip_proj_ctx* c, const RelaxCoef& rc, double
         if (c->env.rb2_log) {  // diagnostics: the loop's launches and stops
             int n1 = 0, n2 = 0;
             for (const Launch& q : log) (q.kind == 1 ? n1 : n2)++;
-            // interior tiles: k_rb2's own predicate (rb2.hpp, `bnd`)
-            int n_int = 0;
+            int n_int = 0;  // interior tiles, by k_rb2's own predicate
             for (int ty = 0; ty < g2.tiles_y; ++ty)
-                for (int tx = 0; tx < g2.tiles_x; ++tx) {
-                    const int ilo = tx * RB2_OX - 4, jlo = ty * RB2_OY - 4;
-                    if (ilo >= 1 && ilo + 2 * RB2_TC - 1 <= g2.nx - 3 && jlo >= 2 &&
-                        jlo + RB2_TR - 1 <= g2.ny - 3)
-                        ++n_int;
-                }
+                for (int tx = 0; tx < g2.tiles_x; ++tx)
+                    n_int += rb2_tile_interior(tx, ty, g2.nx, g2.ny) ? 1 : 0;
             fprintf(stderr, "rb2: iterations %d status %d, k_rb1 %d k_rb2 %d launches, "
                     "%d ambiguous, %d uncertified, res_it %d, kc %d tiles %d x %d x %d "
                     "interior %d\n", r.iterations, r.status, n1, n2, n_ambig, n_uncert,
@@ -1251,412 +1246,20 @@ static void free_ctx(hip_proj_ctx* c) {
     delete c;
 }
 
-// k_ccf's z layers over P planes: runs of kc, and with tail_layers > 0 the
-// last tail_layers layers runs of kc2 (< kc) covering the remaining planes,
-// so the workgroups dispatched last are short and the launch's tail (each CU
-// idles while the last workgroups finish) shrinks. tail_layers = 0: every
-// layer kc.
-static void ccf_layout(SGeo& g, int P, int kc, int kc2, int tail_layers) {
-    kc = std::max(1, std::min(kc, P));
-    g.kc = kc;
-    g.kc2 = kc;
-    g.nz1 = g.tiles_z = (P + kc - 1) / kc;
-    if (tail_layers <= 0 || kc2 <= 0 || kc2 >= kc) return;
-    const int tail = std::min(P, tail_layers * kc2);
-    const int bulk = P - tail;
-    if (bulk <= 0) return;
-    g.kc2 = kc2;
-    g.nz1 = (bulk + kc - 1) / kc;
-    // the bulk's last layer may be partial: the tail then starts at nz1 kc,
-    // past the bulk, and covers P - nz1 kc planes
-    const int rest = std::max(0, P - g.nz1 * kc);
-    g.tiles_z = g.nz1 + (rest + kc2 - 1) / kc2;
-}
-
 static cfd_status_t init_ctx(hip_proj_ctx* c, size_t nx, size_t ny, size_t nz) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, c->device));
     c->grid_cap = std::max(64, prop.multiProcessorCount * 8);
-    // field k starts k x 4 KiB into its allocation (r06): the march reads
-    // r_it and p_{it-1} and writes p_it and r_{it+1} at equal offsets of
-    // different fields, and with every field 2 MiB-aligned those streams meet
-    // on the same HBM channels. 512^3 k_ccf, one box, four interleaved
-    // rounds: 1.026-1.055 ms per iteration against 1.039-1.089 unstaggered
-    // (2 / 1 / 8 KiB: 1.029-1.059 / 1.028-1.067 / 1.029-1.079,
-    // profiles/r06l_ccf_stagger_ab.jsonl; r06k another box, same order).
-    // Textbook CG's sweeps measured 0.8 % slower staggered (1.302-1.335 vs
-    // 1.292-1.302 ms, r06m, where the march gained 1.044-1.048 vs
-    // 1.038-1.062, profiles/r06m_stagger_both_cg_ab.jsonl), so the stagger
-    // is the single-reduction contexts' default only.
-    // CFD_HIP_FIELD_STAGGER=N overrides (0: aligned fields)
-    c->stagger_bytes = (c->cfg.cg_variant == 1) ? 4096 : 0;
-    if (const char* e = getenv("CFD_HIP_FIELD_STAGGER")) c->stagger_bytes = (size_t)atol(e) / 256 * 256;
-    {
-        auto ienv = [](const char* name, int dflt) {
-            const char* e = getenv(name);
-            return e ? atoi(e) : dflt;
-        };
-        c->env.ccf_off = ienv("CFD_HIP_CCF", 1) == 0;
-        c->env.cg_small = ienv("CFD_HIP_CG_SMALL", -1);
-        c->env.rb2_test = ienv("CFD_HIP_RB2_TEST", 0);
-        c->env.rb2_xmap = ienv("CFD_HIP_RB2_XMAP", 0);
-        c->env.rb2_log = getenv("CFD_HIP_RB2_LOG") != nullptr;
-        c->env.rb2 = ienv("CFD_HIP_RB2", 1);
-        c->env.ccf_xmap = ienv("CFD_HIP_CCF_XMAP", 0);
-        c->env.cgb_rev = ienv("CFD_HIP_CGB_REV", 1) != 0;
-        c->env.rb1_pf = ienv("CFD_HIP_RB1_PF", 1) != 0;
-        c->env.rb1_alt = ienv("CFD_HIP_RB1_ALT", 1) != 0;
-        c->env.rb1_fold = ienv("CFD_HIP_RB1_FOLD", 1) != 0;
-        c->env.rk_pair = ienv("CFD_HIP_RK_PAIR", 1) != 0;
-        c->env.alloc_contig = getenv("CFD_HIP_ALLOC") && strcmp(getenv("CFD_HIP_ALLOC"), "contig") == 0;
-        c->env.ccf_edge_side = ienv("CFD_HIP_CCF_EDGE_SIDE", 1) != 0;
-        c->env.ccf_edge_dot = ienv("CFD_HIP_CCF_EDGE_DOT", 1) != 0;
-    }
+    c->env = read_knobs();
     c->nx = nx;
     c->ny = ny;
     c->nz = nz;
-    c->px = (long long)((nx + 7) / 8 * 8);
-    // CFD_HIP_ROW_PAD=N (experiments, r06): N more doubles per row (a
-    // multiple of 8), so that rows do not start on 4 KiB boundaries
-    if (const char* e = getenv("CFD_HIP_ROW_PAD")) c->px += (long long)(std::max(0, atoi(e)) / 8 * 8);
-    c->ps = c->px * (long long)ny;
-    Geo& g = c->geo;
-    g.nx = (int)nx;
-    g.ny = (int)ny;
-    g.nz = (int)nz;
-    g.px = c->px;
-    g.ps = c->ps;
-    g.sz = (nz > 1) ? c->ps : 0;
-    g.k0 = (nz > 1) ? 1 : 0;
-    g.k1 = (nz > 1) ? (int)nz - 1 : 1;
-    g.lo_face = (c->rank == 0) ? 1 : 0;
-    g.hi_face = (c->rank == c->nranks - 1) ? 1 : 0;
-    g.kofs = (int)c->kofs;
-    const int nint_k = g.k1 - g.k0;
-    int kc = 0;
-    if (kc <= 0) {
-        // enough tiles to fill every CU several times, long z runs otherwise
-        long long xy_tiles = (long long)((nx + TX - 1) / TX) * (long long)((ny + TY - 1) / TY);
-        long long want = 4LL * c->grid_cap;
-        kc = (int)std::max<long long>(8, (xy_tiles * nint_k + want - 1) / want);
-        kc = std::min(kc, std::max(1, nint_k));
-    }
-    g.kc = std::max(1, kc);
-    g.tiles_x = (int)((nx + TX - 1) / TX);
-    g.tiles_y = (int)((ny + TY - 1) / TY);
-    g.tiles_z = (nint_k + g.kc - 1) / g.kc;
-
-    // row-pair CG sweeps: 128 x TY x kc tiles (kernels.hpp, k_cgA / k_cgB)
-    c->sweep_ty = (c->cfg.sweep_rows == 4 || c->cfg.sweep_rows == 16) ? c->cfg.sweep_rows : 8;
-    {   // variants built: 0-3 (memory hints), 4 and 7 (+ plane prefetch)
-        const int v = c->cfg.sweep_variant & 63;
-        if (v == 15 && c->sweep_ty >= 8) c->sweep_variant = v;
-        else if ((v == 23 || v == 31) && c->sweep_ty == 16) c->sweep_variant = v;
-        else c->sweep_variant = (v & SW_PREFETCH) ? ((v & 3) == 3 ? 7 : 4) : (v & 3);
-    }
-    {
-        const int vf = c->cfg.sweep_variant_fold;
-        c->sweep_variant_fold = (c->sweep_ty == 16 && (vf == 3 || vf == 11 || vf == 15)) ? vf : 0;
-    }
-    SGeo& sg = c->sgeo;
-    sg.nx = g.nx;
-    sg.ny = g.ny;
-    sg.nz = g.nz;
-    sg.px = g.px;
-    sg.ps = g.ps;
-    sg.sz = g.sz;
-    sg.k0 = g.k0;
-    sg.k1 = g.k1;
-    sg.kofs = g.kofs;
-    sg.tiles_x = (int)((nx + 127) / 128);
-    sg.tiles_y = (int)((ny + c->sweep_ty - 1) / c->sweep_ty);
-    if (c->cfg.kchunk > 0) {
-        sg.kc = c->cfg.kchunk;
-    } else {
-        // long z runs (each chunk re-reads two planes), shortened (down to
-        // 4) until every CU has a workgroup: a thin slab or a mid-size grid
-        // must still fill all 256 CUs. r01f at 512^3: 256-plane runs (256
-        // workgroups) beat 64 by ~2 %; one 8-rank slab: 32 beat 16
-        // (profiles/r01f_sweep_*). r02b: the floor was 16, which left 96^3 /
-        // 128^3 at 36 / 64 workgroups; 4 takes a CG iteration from 53 to
-        // 25 us / 58 to 33 us there (profiles/r02_small_grids.jsonl)
-        sg.kc = 256;
-        const long long want = c->grid_cap / 8;
-        while (sg.kc > 4 &&
-               (long long)sg.tiles_x * sg.tiles_y * ((nint_k + sg.kc - 1) / sg.kc) < want)
-            sg.kc /= 2;
-    }
-    sg.kc = std::max(1, std::min(sg.kc, nint_k));
-    sg.tiles_z = (nint_k + sg.kc - 1) / sg.kc;
-    int n_partials = std::max(c->grid_cap, sg.tiles_x * sg.tiles_y * sg.tiles_z);
-    // single-pass RB-SOR tiling (k_rb1): 124 x 12 cells written per 128 x 16 loaded
-    {
-        SGeo& rg = c->rgeo;
-        rg = sg;
-        // tile width: TC = 64 (128 x 16 cells loaded, 124 x 12 written). The
-        // narrower tiles (32: 64 x 32, 16: 32 x 64) need ~20 % fewer
-        // workgroups at 512^3 and 1024^2 x 512 but mask their halo rows per
-        // lane instead of skipping whole waves, and measured slower (0.846 /
-        // 1.022 vs 0.734 ms at 512^3, profiles/r02_rb_tile_width.jsonl);
-        // CFD_HIP_RB1_TC = 32 / 16 selects them (experiments)
-        int tc = 64;
-        if (const char* e = getenv("CFD_HIP_RB1_TC")) {
-            const int v = atoi(e);
-            if (v == 64 || v == 32 || v == 16) tc = v;
-        }
-        c->rb1_tc = tc;
-        const int ox = 2 * tc - 4, oy = 1024 / tc - 4;
-        rg.tiles_x = (int)((nx - 1 + ox - 1) / ox);
-        rg.tiles_y = (int)((ny - 1 + oy - 1) / oy);
-        rg.kc = 64;
-        if (const char* e = getenv("CFD_HIP_RB1_KC")) rg.kc = std::max(1, atoi(e));  // experiments
-        while (rg.kc > 16 &&
-               (long long)rg.tiles_x * rg.tiles_y * ((nint_k + rg.kc - 1) / rg.kc) < 512)
-            rg.kc /= 2;
-        // small grids: shorter runs (each costs a two-plane prologue) only
-        // while fewer than half the CUs have a workgroup (r02b: 96^3 31 ->
-        // 17 us per iteration at 4 planes; 128^3, 176 workgroups at 16
-        // planes, is slower at 8 or 4; profiles/r02_small_grids.jsonl)
-        while (rg.kc > 4 &&
-               (long long)rg.tiles_x * rg.tiles_y * ((nint_k + rg.kc - 1) / rg.kc) < 128)
-            rg.kc /= 2;
-        rg.kc = std::max(1, std::min(rg.kc, nint_k));
-        rg.tiles_z = (nint_k + rg.kc - 1) / rg.kc;
-        n_partials = std::max(n_partials, rg.tiles_x * rg.tiles_y * rg.tiles_z);
-        // two RB-SOR iterations per sweep (k_rb2, rb2.hpp): 64 x 32 cells
-        // loaded, 56 x 24 written; one device, 3-D. Four partials per
-        // workgroup (two maxima, the value range).
-        SGeo& r2 = c->r2geo;
-        r2 = rg;
-        r2.tiles_x = r2.tiles_y = r2.tiles_z = 0;
-        if (c->nranks == 1 && nz > 1 && nx >= 8 && ny >= 8) {
-            r2.xofs = 0;
-            r2.tiles_x = (int)((nx - 1 + RB2_OX - 1) / RB2_OX);
-            r2.tiles_y = (int)((ny - 1 + RB2_OY - 1) / RB2_OY);
-            // 128-plane z runs: the 6-plane pipeline fill is 4.7 % of a run
-            // (1024^2 x 512: 2.16 -> 2.05 ms per iteration against 64;
-            // 32: 2.34, profiles/r04_rb2_kc.jsonl)
-            r2.kc = 128;
-            // deep grids with many columns: three runs per column (1024^2 x
-            // 512: 170 planes, 2451 workgroups, 1.735-1.739 vs 1.748-1.751 ms
-            // per iteration against 128 in four same-box pairs on two boxes;
-            // 255: 1.78-1.80, 510: 2.02; profiles/r05as_rb2_kc_ab.jsonl)
-            if (nint_k >= 384 &&
-                3LL * r2.tiles_x * r2.tiles_y >= 8LL * std::max(1, c->grid_cap / 8))
-                r2.kc = (nint_k + 2) / 3;
-            if (const char* e = getenv("CFD_HIP_RB2_KC")) r2.kc = std::max(1, atoi(e));
-            // CFD_HIP_RB2_KC_FIXED (tests): the run length as given, so small
-            // grids reach the steady steps of the march (runs of 9+ planes)
-            const bool kc_fixed = getenv("CFD_HIP_RB2_KC_FIXED") != nullptr;
-            while (!kc_fixed && r2.kc > 4 &&
-                   (long long)r2.tiles_x * r2.tiles_y * ((nint_k + r2.kc - 1) / r2.kc) < 512)
-                r2.kc /= 2;
-            r2.kc = std::max(1, std::min(r2.kc, nint_k));
-            r2.tiles_z = (nint_k + r2.kc - 1) / r2.kc;
-            n_partials = std::max(n_partials, 2 * r2.tiles_x * r2.tiles_y * r2.tiles_z);
-        }
-        // the fused single-reduction CG iteration (k_ccf, ccf.hpp): 64 x 32
-        // cells loaded, 60 x 29 written on one device (delta as an edge sum),
-        // 60 x 28 on Z-slabs and with CFD_HIP_CCF_EDGE_DOT=0 (delta = (A r, r)
-        // cell by cell); 3-D
-        c->ccf_edge_dot = c->nranks == 1 && c->env.ccf_edge_dot;
-        const int ccf_oy = c->ccf_edge_dot ? CCF_OY_EDGE : CCF_OY;
-        SGeo& cg = c->ccgeo;
-        cg = rg;
-        cg.tiles_x = cg.tiles_y = cg.tiles_z = 0;
-        if (nz >= 3 && nx >= 4 && ny >= 4) {
-            cg.xofs = 0;
-            cg.tiles_x = (int)((nx - 1 + CCF_OX - 1) / CCF_OX);
-            cg.tiles_y = (int)((ny - 1 + ccf_oy - 1) / ccf_oy);
-            // z-run length: 24 planes on deep grids, 16 on thin ones (r05;
-            // r04 had 32). 512^3 on one device: 24 at 1.048-1.049 vs 32's
-            // 1.059 ms per iteration in every stable pair on two boxes (20 and
-            // 28 equal to 24, 40 slower; profiles/r05ao_ccf_kc_ab.jsonl). The
-            // rank-0 slab shapes of 2 / 4 / 8 ranks, 512^2 x 257 / 130 / 66:
-            // 16 at 0.600-0.604 / 0.316-0.319 / 0.171 ms against 24's 0.613-
-            // 0.615 / 0.317-0.318 / 0.169 and 32's 0.627-0.630 / 0.334-0.335 /
-            // 0.197 (profiles/r05at_ccf_kc_thin_ab.jsonl)
-            // r06: one device always 24 (256^3: 0.151-0.157 vs 16's 0.159-0.168
-            // ms per iteration in three same-box pairs, profiles/r06c_ccf_kc_256_ab.jsonl;
-            // the 16 of r05 was measured on 512^2 slab shapes only);
-            // Z-slabs: 16, and 11 on slabs of <= 100 planes (512^2 x 66, the
-            // 8-rank slab: 0.1615-0.1678 vs 16's 0.1706-0.1712, 13 0.1637-0.1693,
-            // 21 0.168, 32 0.189-0.197; profiles/r06c_ccf_kc_slab8_ab.jsonl)
-            cg.kc = (c->nranks == 1) ? 24 : (nint_k <= 100 ? 11 : 16);
-            const char* ekc = getenv("CFD_HIP_CCF_KC");  // experiments
-            if (ekc) cg.kc = std::max(1, atoi(ekc));
-            const bool kc_fixed = getenv("CFD_HIP_CCF_KC_FIXED") != nullptr;
-            while (!kc_fixed && cg.kc > 4 &&
-                   (long long)cg.tiles_x * cg.tiles_y * ((nint_k + cg.kc - 1) / cg.kc) < 512)
-                cg.kc /= 2;
-            // tail layers of shorter runs (experiments: CFD_HIP_CCF_TAIL = layers,
-            // CFD_HIP_CCF_KC2 = their run length; default off)
-            const int tail_l = getenv("CFD_HIP_CCF_TAIL") ? atoi(getenv("CFD_HIP_CCF_TAIL")) : 0;
-            const int kc2 = getenv("CFD_HIP_CCF_KC2") ? atoi(getenv("CFD_HIP_CCF_KC2")) : cg.kc / 2;
-            c->ccf_tail = tail_l;
-            c->ccf_kc2 = kc2;
-            ccf_layout(cg, nint_k, cg.kc, kc2, tail_l);
-            n_partials = std::max(n_partials, cg.tiles_x * cg.tiles_y * cg.tiles_z);
-            // Z-slabs of >= 3 planes: the edge planes' launch (kmode 1) and
-            // the interior planes' (kmode 2), so the r halo overlaps the latter
-            c->cc_edge = c->cc_int = cg;
-            c->cc_edge.tiles_x = c->cc_int.tiles_x = 0;
-            if (c->nranks > 1 && nint_k >= 3) {
-                SGeo& e = c->cc_edge;
-                SGeo& m = c->cc_int;
-                e = m = cg;
-                e.kmode = 1;
-                e.kc = 1;
-                e.tiles_z = 2;
-                m.kmode = 2;
-                m.kt0 = cg.k0 + 1;
-                m.kt1 = cg.k1 - 1;
-                ccf_layout(m, m.kt1 - m.kt0, cg.kc, c->ccf_kc2, c->ccf_tail);
-                // fused form: the interior march with stage c (cc_int_red)
-                // and k_cc2 on the two edge planes (cc2_edge, the row-pair
-                // tiling of k_cc2 in kmode 1) share one reduction, the
-                // interior workgroups' partials first
-                const char* ef = getenv("CFD_HIP_CCF_SLAB_FUSED");
-                if (!(ef && atoi(ef) == 0)) {
-                    SGeo& ir = c->cc_int_red;
-                    SGeo& ee = c->cc2_edge;
-                    ir = m;
-                    ee = sg;
-                    ee.kmode = 1;
-                    ee.kc = 1;
-                    ee.tiles_z = 2;
-                    const int ni = ir.tiles_x * ir.tiles_y * ir.tiles_z;
-                    const int ne = ee.tiles_x * ee.tiles_y * ee.tiles_z;
-                    ir.part_ofs = 0;
-                    ee.part_ofs = ni;
-                    ir.part_total = ee.part_total = ni + ne;
-                    n_partials = std::max(n_partials, ni + ne);
-                }
-            }
-        }
-        // the last x tile of a TC-64 launch is partial unless 124 divides the
-        // row: its workgroups run a full tile's steps for a few columns
-        // (512^3: 14 of 124). Up to 28 such columns run instead as a strip
-        // of TC-16 tiles (28 columns x 60 rows, 4.8x fewer workgroups) in
-        // the same grid (k_rb1m). CFD_HIP_RB1_STRIP=0: off.
-        const char* estrip = getenv("CFD_HIP_RB1_STRIP");
-        c->rb_strip_tc = 0;
-        if (tc == 64 && c->nranks == 1 && !(estrip && atoi(estrip) == 0)) {
-            const int T = (int)(nx / 124), R = (int)nx - 124 * T;
-            // TC-32 strips (R in 29..60) measured slower (1024^2 x 512: 2.96 vs
-            // 2.93 ms); TC-16 ones faster (512^3: 0.734 vs 0.760 ms,
-            // profiles/r03_rb1_strip.jsonl)
-            // R = 1 (nx = 124 T + 1): the T full tiles already store every
-            // pair (cell nx - 1 is the Neumann mirror), so no strip
-            const int stc = (R >= 2 && R <= 28) ? 16 : 0;
-            if (stc) {
-                c->rb_strip_tc = stc;
-                SGeo& m = c->rg_main;
-                SGeo& q = c->rg_strip;
-                m = rg;
-                m.tiles_x = T;
-                q = rg;
-                q.xofs = 124 * T;
-                q.tiles_x = 1;
-                const int oy = 1024 / stc - 4;
-                q.tiles_y = (int)((ny - 1 + oy - 1) / oy);
-                q.kc = std::max(1, std::min(rg.kc, nint_k));
-                q.tiles_z = (nint_k + q.kc - 1) / q.kc;
-                // one grid (k_rb1m): partial slot = blockIdx.x, total = gridDim.x
-                m.part_ofs = q.part_ofs = 0;
-                m.part_total = q.part_total = 0;
-                n_partials = std::max(n_partials, m.tiles_x * m.tiles_y * m.tiles_z +
-                                                      q.tiles_x * q.tiles_y * q.tiles_z);
-            }
-        }
-        // Z-slabs: output planes k0+1 .. k1-2 split into two halves around
-        // the edge planes (relax_solve_fused); CFD_HIP_RB_SPLIT=0 keeps the
-        // one-launch iteration with blocking exchanges (A/B)
-        const char* es = getenv("CFD_HIP_RB_SPLIT");
-        c->split_rb = (c->nranks > 1 && nint_k >= 4 && !(es && atoi(es) == 0)) ? 1 : 0;
-        if (c->split_rb) {
-            const int a0 = g.k0 + 1, a1 = g.k1 - 1;  // interior output planes [a0, a1)
-            const int mid = a0 + (a1 - a0) / 2;
-            auto range = [&](SGeo& q, int lo, int hi) {
-                q = rg;
-                q.kmode = 2;
-                q.kt0 = lo;
-                q.kt1 = hi;
-                q.kc = std::max(1, std::min(rg.kc, hi - lo));
-                q.tiles_z = (hi - lo + q.kc - 1) / q.kc;
-            };
-            range(c->rg_in1, a0, mid);
-            range(c->rg_in2, mid, a1);
-            c->rg_edge = rg;
-            c->rg_edge.kmode = 1;
-            c->rg_edge.kc = 1;
-            c->rg_edge.tiles_z = 2;
-            const int xy = rg.tiles_x * rg.tiles_y;
-            const int n1 = xy * c->rg_in1.tiles_z, ne = xy * 2, n2 = xy * c->rg_in2.tiles_z;
-            c->rg_in1.part_ofs = 0;
-            c->rg_edge.part_ofs = n1;
-            c->rg_in2.part_ofs = n1 + ne;
-            c->rg_in1.part_total = c->rg_edge.part_total = c->rg_in2.part_total = n1 + ne + n2;
-            n_partials = std::max(n_partials, n1 + ne + n2);
-        }
-    }
-    {   // predictor / corrector: 128 x PR_TY x kc tiles, >= ~8 workgroups per CU
-        SGeo& pg = c->pgeo;
-        pg = sg;
-        pg.kmode = 0;
-        pg.tiles_x = (int)((nx + 127) / 128);
-        pg.tiles_y = (int)((ny + PR_TY - 1) / PR_TY);
-        const long long xy = (long long)pg.tiles_x * pg.tiles_y;
-        const long long zt = std::max(1LL, (4LL * c->grid_cap / PR_TY + xy - 1) / xy);
-        pg.kc = (int)std::max<long long>(1, (nint_k + zt - 1) / zt);
-        pg.tiles_z = (nint_k + pg.kc - 1) / pg.kc;
-        // k_pred3 / k_corr3: the CG sweeps' 128 x 16 tiles, long z runs
-        // shortened until every CU has a workgroup (one 1024-thread
-        // workgroup per CU: 110 KB of LDS)
-        SGeo& p3 = c->pgeo16;
-        p3 = sg;
-        p3.kmode = 0;
-        p3.tiles_x = (int)((nx + 127) / 128);
-        p3.tiles_y = (int)((ny + PC_TY - 1) / PC_TY);
-        p3.kc = 256;
-        while (p3.kc > 4 && (long long)p3.tiles_x * p3.tiles_y * ((nint_k + p3.kc - 1) / p3.kc) <
-                                c->grid_cap / 8)
-            p3.kc /= 2;
-        p3.kc = std::max(1, std::min(p3.kc, nint_k));
-        p3.tiles_z = (nint_k + p3.kc - 1) / p3.kc;
-        // default k_pred3 / k_corr3 (r03: predictor 1.47 -> 1.25 ms, fetch
-        // 45.7 -> 25.6 B/cell at 512^3, profiles/r03_pc3.jsonl);
-        // CFD_HIP_PC3=0 selects k_pred2 / k_corr2
-        c->pc3 = 1;
-        if (const char* e = getenv("CFD_HIP_PC3")) {  // A/B: k_pred3 / k_corr3 (ctx.hpp)
-            const int v = atoi(e);
-            c->pc3 = (v == 1 || v == 2 || v == 4) ? v : 0;
-        }
-    }
-    c->split_b = (c->nranks > 1 && nint_k >= 3) ? 1 : 0;
-    if (c->split_b) {
-        // sweep B on slabs: the two edge planes (what the neighbours need)
-        // first, then planes k0+1 .. k1-1; one reduction over both launches
-        SGeo& e = c->sg_edge;
-        SGeo& m = c->sg_int;
-        e = sg;
-        e.kmode = 1;
-        e.kc = 1;
-        e.tiles_z = 2;
-        m = sg;
-        m.k0 = sg.k0 + 1;
-        m.k1 = sg.k1 - 1;
-        m.kc = std::max(1, std::min(sg.kc, m.k1 - m.k0));
-        m.tiles_z = (m.k1 - m.k0 + m.kc - 1) / m.kc;
-        const int ne = e.tiles_x * e.tiles_y * e.tiles_z;
-        const int nm = m.tiles_x * m.tiles_y * m.tiles_z;
-        e.part_ofs = 0;
-        m.part_ofs = ne;
-        e.part_total = m.part_total = ne + nm;
-        n_partials = std::max(n_partials, ne + nm);
-    }
+    // every launch geometry of this context (tile_plan.hpp)
+    const PlanIn in{nx, ny, nz, c->rank, c->nranks, c->kofs, c->grid_cap, c->cfg.sweep_rows,
+                    c->cfg.sweep_variant, c->cfg.kchunk, c->cfg.cg_variant};
+    static_cast<TilePlan&>(*c) = plan_tiles(in, c->env);
 
     const size_t n = field_elems(c);
     double** fields[] = {&c->u, &c->v, &c->w, &c->p, &c->us, &c->vs, &c->ws, &c->pn,
@@ -1674,9 +1277,7 @@ static cfd_status_t init_ctx(hip_proj_ctx* c, size_t nx, size_t ny, size_t nz) {
     HIP_TRY(hipMalloc((void**)&c->st, sizeof(CgState)));
     HIP_TRY(hipMemsetAsync(c->st, 0, sizeof(CgState), c->stream));
     // x2: the single-reduction CG reduces two values per workgroup
-    // k_cg_small indexes its two partial slots by CGS_MAX_WG whatever the CU count
-    n_partials = std::max(n_partials, CGS_MAX_WG);
-    HIP_TRY(hipMalloc((void**)&c->partials, 2 * sizeof(double) * n_partials));
+    HIP_TRY(hipMalloc((void**)&c->partials, 2 * sizeof(double) * c->n_partials));
     HIP_TRY(hipMalloc((void**)&c->counter, 64));
     HIP_TRY(hipMemsetAsync(c->counter, 0, 64, c->stream));
     HIP_TRY(hipMalloc((void**)&c->red, 8 * sizeof(unsigned long long)));
@@ -1873,22 +1474,10 @@ static hip_proj_ctx* create_common(size_t nx, size_t ny, size_t nz_local, size_t
         return nullptr;
     }
     // placement draws of the single-reduction CG's fields (3-D contexts of
-    // >= 2^24 cells, one device or one Z-slab rank; see placement_draws)
+    // >= 2^24 cells, one device or one Z-slab rank; see placement_draws and,
+    // for the pool's size, Knobs::placement_draws)
     {
-        // a pool of 6 allocated sets and 40 probes: the 6 sets as allocated,
-        // then 34 random assignments of pool buffers to the seven roles.
-        // r06x, 512^3, contexts of one process (ms per iteration): none
-        // 1.109-1.201; 8 sets 1.037-1.126; 2 sets + 16 probes 1.033-1.047
-        // with one 1.198 (a pool with no good pair); 4 sets + 16 probes
-        // 1.030-1.044 (profiles/r06x_placement_strategies.jsonl). r06ar,
-        // twelve contexts each: 4 sets + 24 probes 1.034-1.048 (mean
-        // 1.0400), 6 + 40 1.032-1.042 (1.0372), 4 + 48 1.036-1.061
-        // (profiles/r06ar_placement_draws.jsonl); ~0.3 s more per context.
-        // CFD_HIP_PLACEMENT_DRAWS = sets (1: off), _TRIALS = probes
-        const char* e = getenv("CFD_HIP_PLACEMENT_DRAWS");
-        const int draws = e ? atoi(e) : 6;
-        const char* et = getenv("CFD_HIP_PLACEMENT_TRIALS");
-        const int trials = et ? std::max(1, atoi(et)) : 40;
+        const int draws = c->env.placement_draws, trials = c->env.placement_trials;
         const long long cells = (long long)nx * (long long)ny * (long long)nz_local;
         if (c->cfg.cg_variant == 1 && nz_local >= 3 && cells >= (1LL << 24) && draws > 1 &&
             c->ccgeo.tiles_x > 0 && !c->env.ccf_off) {
@@ -1935,16 +1524,7 @@ hip_proj_ctx_t* hip_proj_create(size_t nx, size_t ny, size_t nz, const hip_proj_
 
 cfd_status_t hip_proj_slab_layout(size_t nz, int rank, int size, size_t* k_offset,
                                   size_t* nz_local) {
-    if (nz < 3 || size < 1 || rank < 0 || rank >= size || (size_t)size > nz - 2)
-        return CFD_ERROR_INVALID;
-    // interior planes 1..nz-2 split as evenly as possible, lower ranks first
-    const size_t nint = nz - 2, base = nint / (size_t)size, rem = nint % (size_t)size;
-    const size_t r = (size_t)rank;
-    const size_t first = 1 + r * base + std::min(r, rem);
-    const size_t count = base + (r < rem ? 1 : 0);
-    if (k_offset) *k_offset = first - 1;
-    if (nz_local) *nz_local = count + 2;
-    return CFD_SUCCESS;
+    return slab_layout(nz, rank, size, k_offset, nz_local) ? CFD_SUCCESS : CFD_ERROR_INVALID;
 }
 
 hip_proj_ctx_t* hip_proj_create_slab(size_t nx, size_t ny, size_t nz, hip_proj_comm_t* comm,

@@ -68,10 +68,7 @@ namespace cfdhip {
 #define CFD_RB2_DIAG 0
 #endif
 constexpr bool RB2_DIAG = CFD_RB2_DIAG != 0;
-constexpr int RB2_TC = 32;   // x pairs per tile row
-constexpr int RB2_TR = 32;   // tile rows (two per wave)
-constexpr int RB2_OX = 56;   // columns written per tile
-constexpr int RB2_OY = 24;   // rows written per tile
+// RB2_TC x RB2_TR pairs x rows loaded, RB2_OX x RB2_OY cells written: tile_plan.hpp
 constexpr int ST_RB2_AMBIG = 10;   // a decision within the approximation bound (host resolves)
 constexpr int ST_RB2_UNCERT = 11;  // a value outside the certified range (host reruns exactly)
 
@@ -653,6 +650,8 @@ static __global__ __launch_bounds__(1024, 4) void k_rb2(SGeo g, Rb2Coef cf,
     const int ke = min(kb + g.kc, g.k1);
     // does the tile touch the faces (its loaded cells reach i < 1,
     // i > nx - 3, j < 2 or j > ny - 3)?
+    // (rb2_tile_interior of tile_plan.hpp, spelt out: the call compiles to
+    // other device code)
     const int ilo = tx * RB2_OX - 4, jlo = ty * RB2_OY - 4;
     const bool bnd = !(ilo >= 1 && ilo + 2 * RB2_TC - 1 <= g.nx - 3 && jlo >= 2 &&
                        jlo + RB2_TR - 1 <= g.ny - 3);

@@ -25,8 +25,11 @@ import numpy as np
 
 LD = np.longdouble
 
-# the k_ccf tile (ccf.hpp CCF_OX x CCF_OY; z runs of kc planes), the textbook
-# sweeps' (128 columns x sweep_rows) and k_pred3 / k_corr3's (128 x 16)
+# the k_ccf tiles (tile_plan.hpp; z runs of kc planes): CCF_OX x CCF_OY_EDGE on
+# one device (the edge-sum form), CCF_OX x CCF_OY on Z-slabs and with
+# CFD_HIP_CCF_EDGE_DOT=0 (the cell form); the textbook sweeps' (128 columns x
+# sweep_rows) and k_pred3 / k_corr3's (128 x 16)
+CCF_EDGE_TILE = (60, 29)
 CCF_TILE = (60, 28)
 SWEEP_TILE = (128,)
 PC3_TILE = (128, 16)

@@ -2,12 +2,16 @@
 saying which tile seam the shape sits on, and the random problem every test
 of a shape shares (test_cg_reference.py, test_gpu_cg_seams.py).
 
-Tilings (cfd_amd/csrc/hip):
-  k_ccf          60 x 28 cells written per tile (ccf.hpp CCF_OX / CCF_OY), tile
-                 tx writes columns 60 tx .. 60 tx + 59, ty rows 28 ty .. 28 ty
-                 + 27; tiles_x = (nx - 1 + 59) / 60; z runs of kc planes from
-                 plane 1 (kc = 24 on one device, halved down to 3 on small
-                 grids unless CFD_HIP_CCF_KC_FIXED is set)
+Tilings (cfd_amd/csrc/hip/tile_plan.hpp, plan_tiles; tests/test_tile_plan.py
+holds the claims below to what that planner gives, without a GPU):
+  k_ccf          one device: 60 x 29 cells written per tile (CCF_OX x
+                 CCF_OY_EDGE, the edge-sum form), tile tx writes columns
+                 60 tx .. 60 tx + 59, ty rows 29 ty .. 29 ty + 28; on Z-slabs
+                 and with CFD_HIP_CCF_EDGE_DOT=0 (the cell form) 60 x 28
+                 (CCF_OY), rows 28 ty .. 28 ty + 27; tiles_x = (nx - 1 + 59) /
+                 60; z runs of kc planes from plane 1 (kc = 24 on one device,
+                 halved down to 3 on small grids unless CFD_HIP_CCF_KC_FIXED
+                 is set)
   k_cgA / k_cgB  128 columns x sweep_rows (8 or 16) rows, z runs of kchunk
   k_cg_small     a flat index over the interior, 256 threads per workgroup
   k_pred3/corr3  128 columns x 16 rows
@@ -30,35 +34,53 @@ ITERS = (1, 3, 4, 5, 8)  # every residue of the CG_XFOLD = 4 fold period + the f
 BAR = 1e-11
 MAX_CELLS = 340_000
 CG_SMALL_CELLS = 300_000  # kernels.hpp
+CELL_FORM = " | 28-row tiles: "  # splits a description, see CCF_FIXED
 
-# cg_variant 1, 3-D, CFD_HIP_CCF_KC_FIXED=1: 24-plane runs
+# cg_variant 1, 3-D, CFD_HIP_CCF_KC_FIXED=1: 24-plane runs. The y seams of this
+# table are those of the cell form's 28-row tiles only: it was chosen when
+# every context ran that form. test_gpu_cg_seams.py creates one-device contexts
+# with the default switches, which now run the edge-sum form on 29-row tiles, so
+# there these shapes sit on the x seams and the z runs named before CELL_FORM,
+# and what follows it holds on the 28-row tiles (CFD_HIP_CCF_EDGE_DOT=0, and
+# the slabs' march). The 29-row seams are test_gpu_ccf_edge_dot.EDGE_FIXED's.
+# "n-column" / "n-row": the last tile's interior columns / rows.
 CCF_FIXED = [
-    ((60, 28, 26), "wall column 59 and wall row 27 close tile 0; 24 planes: exactly one run"),
-    ((61, 29, 26), "last interior column 59 / row 27 close tile 0, the walls have no tile"),
-    ((62, 30, 26), "one-column last tile (interior 60 + wall 61), two-row last tile"),
-    ((63, 31, 26), "last x tile: interior 60-61 + wall 62; last y tile likewise"),
-    ((121, 57, 26), "three-tile seams: last interior column 119 / row 55 close tile 1"),
-    ((122, 58, 27), "one-column third x tile, two-row third y tile; runs 24 + 1"),
+    ((60, 28, 26), "wall column 59 closes tile 0; 24 planes: exactly one run" + CELL_FORM +
+                   "wall row 27 closes tile 0"),
+    ((61, 29, 26), "last interior column 59 closes tile 0, the wall has no tile" + CELL_FORM +
+                   "last interior row 27 closes tile 0"),
+    ((62, 30, 26), "one-column last x tile (interior 60 + wall 61)" + CELL_FORM +
+                   "one-row last y tile (interior 28 + wall 29)"),
+    ((63, 31, 26), "last x tile: interior 60-61 + wall 62" + CELL_FORM +
+                   "last y tile likewise (interior 28-29 + wall 30)"),
+    ((121, 57, 26), "second seam: last interior column 119 closes tile 1" + CELL_FORM +
+                    "last interior row 55 closes tile 1"),
+    ((122, 58, 27), "one-column third x tile; runs 24 + 1" + CELL_FORM + "one-row third y tile"),
     ((60, 29, 27), "even nx clamp with the wall on the seam; runs 24 + 1"),
-    ((61, 28, 27), "odd nx clamp, wall row on the y seam; runs 24 + 1"),
+    ((61, 28, 27), "odd nx clamp; runs 24 + 1" + CELL_FORM + "wall row on the y seam"),
     ((62, 31, 28), "one-column last x tile; runs 24 + 2"),
-    ((63, 30, 28), "two-column last x tile, one-row last y tile; runs 24 + 2"),
+    ((63, 30, 28), "two-column last x tile; runs 24 + 2" + CELL_FORM + "one-row last y tile"),
     ((61, 29, 51), "49 planes: two runs + one plane"),
-    ((62, 30, 51), "one-column / one-row last tiles over two runs + one plane"),
-    ((60, 58, 28), "x wall on the seam, three y tiles; runs 24 + 2"),
-    ((121, 28, 27), "x interior ends on the second seam, y wall on the first"),
+    ((62, 30, 51), "one-column last x tile over two runs + one plane" + CELL_FORM +
+                   "one-row last y tile"),
+    ((60, 58, 28), "x wall on the seam, two y tiles; runs 24 + 2" + CELL_FORM + "three y tiles"),
+    ((121, 28, 27), "x interior ends on the second seam" + CELL_FORM + "y wall on the first"),
     ((122, 31, 28), "three x tiles (one column), two y tiles; runs 24 + 2"),
-    ((63, 57, 27), "y interior ends on the second seam; runs 24 + 1"),
-    ((62, 58, 27), "one-column x tile, two-row third y tile (also a step shape)"),
-    ((61, 30, 27), "x interior ends on the seam, one-row last y tile (also a step shape)"),
+    ((63, 57, 27), "runs 24 + 1" + CELL_FORM + "y interior ends on the second seam"),
+    ((62, 58, 27), "one-column last x tile (also a step shape)" + CELL_FORM +
+                   "one-row third y tile"),
+    ((61, 30, 27), "x interior ends on the seam (also a step shape)" + CELL_FORM +
+                   "one-row last y tile"),
     ((121, 30, 51), "two full x tiles over two runs + one plane"),
 ]
-# cg_variant 1 under the default kc (halved to 3 at these sizes)
+# cg_variant 1 under the default kc (halved to 3 at these sizes, then clamped
+# to the planes there are)
 CCF_DEFAULT = [
     ((4, 4, 3), "the smallest legal grid: 2 x 2 x 1 interior cells"),
     ((5, 4, 3), "odd nx at the smallest ny, nz"),
     ((4, 5, 4), "even nx, two interior planes"),
-    ((62, 30, 27), "the product's short runs (kc = 3) on the one-column / one-row tiles"),
+    ((62, 30, 27), "the product's short runs (kc = 3) on the one-column last x tile" + CELL_FORM +
+                   "one-row last y tile"),
 ]
 # textbook CG: the sweeps (CFD_HIP_CG_SMALL=0, sweep_rows 8 and 16) and, by
 # default, k_cg_small
@@ -96,8 +118,8 @@ STEP_SHAPES = [
     ((130, 18, 7), "one interior column / two rows past the 128 x 16 tile"),
     ((129, 17, 5), "wall-only x and y tiles"),
     ((127, 33, 6), "odd nx short of the seam, wall-only third y tile"),
-    ((61, 30, 27), "k_ccf: x interior ends on the seam, one-row last y tile"),
-    ((62, 58, 27), "k_ccf: one-column x tile, two-row third y tile"),
+    ((61, 30, 27), "k_ccf: x interior ends on the seam" + CELL_FORM + "one-row last y tile"),
+    ((62, 58, 27), "k_ccf: one-column last x tile" + CELL_FORM + "one-row third y tile"),
 ]
 # Z-slabs (in-process groups): (shape, ranks, interior planes per rank)
 SLAB_CASES = [

@@ -8,6 +8,7 @@ reference build); these fixtures freeze its full-field outputs so the GPU
 tests can check the HIP path against stored data as well as the live oracle.
 
 usage: python tests/golden/make_golden.py      (writes *.npz next to this file)
+       python tests/golden/make_golden.py tile_plans   (tile_plans.json, from the planner)
 """
 import sys
 from pathlib import Path
@@ -296,7 +297,21 @@ def reference_abi(include_dir: str):
     (HERE / "reference_abi_digests.json").write_text(json.dumps(rec, indent=1) + "\n")
 
 
+def tile_plans():
+    """tile_plans.json: a digest of the plan of every case of
+    tests/tile_plan_cases.py, as tests/native/tile_plan_dump.cpp prints it from the product's planner
+    (cfd_amd/csrc/hip/tile_plan.hpp). For a DELIBERATE change of the tiling
+    only: tests/test_tile_plan.py pins the planner to this file."""
+    from tests import tile_plan_cases
+
+    n = tile_plan_cases.write_fixture()
+    print(tile_plan_cases.FIXTURE.name, n, "cases", tile_plan_cases.FIXTURE.stat().st_size)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["tile_plans"]:
+        tile_plans()
+        sys.exit(0)
     if sys.argv[1:2] == ["reference_abi"]:
         reference_abi(sys.argv[2])
         sys.exit(0)

@@ -2,14 +2,16 @@
 layout each one gives the kernel, and the random problems the tests share
 (test_rb2_shapes.py on the CPU, test_gpu_rb2_interior.py on the GPU).
 
-What is restated here (cfd_amd/csrc/hip):
-  projection_hip.hip, the r2geo block
+What is restated here (cfd_amd/csrc/hip), as the independent model the GPU
+tests compare the launch log with; tests/test_tile_plan.py holds layout() and
+is_interior() to the product's planner without a GPU:
+  tile_plan.hpp, plan_rb2 (the r2geo tiling)
       tiles of 56 x 24 written cells (RB2_OX x RB2_OY) from cell 0,
       tiles_x = (nx - 1 + 55) / 56; z runs of kc planes from plane 1: 128
       (or (nint_k + 2) / 3 on deep, wide grids), CFD_HIP_RB2_KC in its place,
       halved while kc > 4 and there are fewer than 512 workgroups unless
       CFD_HIP_RB2_KC_FIXED is set, then clamped to [1, nz - 2]
-  rb2.hpp, k_rb2
+  tile_plan.hpp, rb2_tile_interior (k_rb2 spells the same test out)
       a tile loads 64 x 32 cells from (56 tx - 4, 24 ty - 4) and is interior
       (rb2_march<BND = false>) when those are columns 1 .. nx - 3 and rows
       2 .. ny - 3 at most
@@ -58,7 +60,7 @@ class Layout(NamedTuple):
 
 
 def is_interior(tx, ty, nx, ny):
-    """k_rb2's `!bnd`."""
+    """rb2_tile_interior (k_rb2's `!bnd`)."""
     ilo, jlo = tx * OX - 4, ty * OY - 4
     return ilo >= 1 and ilo + LX - 1 <= nx - 3 and jlo >= 2 and jlo + LY - 1 <= ny - 3
 

@@ -7,7 +7,9 @@ right-hand side is N(0, 1), the initial iterate 0.1 N(0, 1) with its own
 Neumann shell, dx != dy != dz, and the shapes put the wall, the last interior
 column / row / plane and one-cell last tiles on the seams of
 
-  k_ccf (cg_variant 1)     60 x 28 x kc tiles, 24-plane runs + short remainder
+  k_ccf (cg_variant 1)     60 x 29 x kc tiles on one device, 60 x 28 x kc on
+                           slabs (cg_seam_shapes.CCF_FIXED says which seams
+                           that leaves here), 24-plane runs + short remainder
                            runs, the smallest legal grids
   k_cgA / k_cgB            128 x 8 and 128 x 16 tiles, a kchunk remainder run
   k_cg_small               the same shapes, a ragged last workgroup, the
@@ -99,12 +101,12 @@ def _capped_solves(shape, what, tile, kc=None, timers=None, **cfg):
 @pytest.mark.parametrize("shape", [s for s, _ in T.CCF_FIXED], ids=T.sid)
 def test_ccf_24_plane_runs(hip_lib, monkeypatch, shape):
     monkeypatch.setenv("CFD_HIP_CCF_KC_FIXED", "1")
-    _capped_solves(shape, "k_ccf kc 24", R.CCF_TILE, 24, **CC)
+    _capped_solves(shape, "k_ccf kc 24", R.CCF_EDGE_TILE, 24, **CC)
 
 
 @pytest.mark.parametrize("shape", [s for s, _ in T.CCF_DEFAULT], ids=T.sid)
 def test_ccf_default_runs(hip_lib, shape):
-    _capped_solves(shape, "k_ccf default kc", R.CCF_TILE, 3, **CC)
+    _capped_solves(shape, "k_ccf default kc", R.CCF_EDGE_TILE, 3, **CC)
 
 
 @pytest.mark.parametrize("rows", [8, 16])
@@ -135,7 +137,7 @@ def test_single_reduction_2d(hip_lib, shape):
 def test_paths_taken(hip_lib, monkeypatch):
     """The cases above run the kernels they name: launch counts of one timed
     context per family (timing changes no result; the gates hold here too)."""
-    _capped_solves((62, 30, 27), "k_ccf timed", R.CCF_TILE, 3,
+    _capped_solves((62, 30, 27), "k_ccf timed", R.CCF_EDGE_TILE, 3,
                    timers={"cc_fused": True, "cc_fold": True, "cc_update": False,
                            "cg_sweep_a": False, "cg_small": False}, **CC)
     _capped_solves((62, 30, 1), "k_cc1/k_cc2 timed", (128, 16),
