@@ -10,6 +10,7 @@ import torch
 
 from cfd_amd import _abi as A
 from cfd_amd import _native, api
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -33,7 +34,7 @@ def test_scalar_and_velocity_bcs_bitwise(hip_lib, shape, bc):
     d = _dev(a)
     hip_lib.bc_apply_scalar_3d_gpu(C.c_void_p(d.data_ptr()), nx, ny, nz, bc, _stream())
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(d.cpu().numpy(), ref)
+    assert_bits_equal(d.cpu().numpy(), ref)
     # velocity form: u, v, w each get the scalar BC
     us = [rng.standard_normal(shape) for _ in range(3)]
     ds = [_dev(u) for u in us]
@@ -44,7 +45,7 @@ def test_scalar_and_velocity_bcs_bitwise(hip_lib, shape, bc):
         r = u.copy()
         if nz > 1 or x is not ds[2]:
             api.bc_apply_scalar_3d(r, bc)
-        np.testing.assert_array_equal(x.cpu().numpy(), r)
+        assert_bits_equal(x.cpu().numpy(), r)
 
 
 def test_dirichlet_2d_bitwise(hip_lib):
@@ -60,7 +61,7 @@ def test_dirichlet_2d_bitwise(hip_lib):
     hip_lib.bc_apply_dirichlet_scalar_gpu(C.c_void_p(d.data_ptr()), nx, ny, C.byref(vals),
                                           _stream())
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(d.cpu().numpy(), ref)
+    assert_bits_equal(d.cpu().numpy(), ref)
     u, v = _dev(a), _dev(-a)
     vv = api.dirichlet(top=7.0)
     hip_lib.bc_apply_dirichlet_velocity_gpu(C.c_void_p(u.data_ptr()), C.c_void_p(v.data_ptr()),
@@ -68,8 +69,8 @@ def test_dirichlet_2d_bitwise(hip_lib):
     torch.cuda.synchronize()
     rv = -a
     host.bc_apply_dirichlet_scalar_3d(rv.ctypes.data_as(A.c_double_p), nx, ny, 1, 0, C.byref(vv))
-    np.testing.assert_array_equal(u.cpu().numpy(), ref)
-    np.testing.assert_array_equal(v.cpu().numpy(), rv)
+    assert_bits_equal(u.cpu().numpy(), ref)
+    assert_bits_equal(v.cpu().numpy(), rv)
 
 
 def test_degenerate_sizes_are_no_ops(hip_lib):
@@ -79,4 +80,4 @@ def test_degenerate_sizes_are_no_ops(hip_lib):
     hip_lib.bc_apply_scalar_3d_gpu(C.c_void_p(d.data_ptr()), 5, 5, 2, A.BC_TYPE_NEUMANN, None)
     hip_lib.bc_apply_scalar_gpu(C.c_void_p(d.data_ptr()), 2, 25, A.BC_TYPE_NEUMANN, None)
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(d.cpu().numpy(), a)
+    assert_bits_equal(d.cpu().numpy(), a)

@@ -12,6 +12,7 @@ from cfd_amd import _abi as A
 from cfd_amd import api
 from oracle import oracle
 from tests import cases, dvd
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -58,7 +59,7 @@ def test_thermal_bcs_bitwise(hip_lib, shape, types):
     got = ctx.get_field(A.HIP_FIELD_T)
     ctx.close()
     assert oracle.apply_thermal_bcs(f, p) == A.CFD_SUCCESS
-    np.testing.assert_array_equal(got, f.T)
+    assert_bits_equal(got, f.T)
 
 
 def _steps(g, f, p, n, method=A.HIP_POISSON_CG, **cfg):
@@ -110,7 +111,7 @@ def test_energy_steps_rbsor_bitwise(hip_lib):
     finally:
         oracle.set_projection_poisson_params(None)
     for k in ("u", "v", "w", "p", "T"):
-        np.testing.assert_array_equal(getattr(f, k), getattr(fo, k), err_msg=k)
+        assert_bits_equal(getattr(f, k), getattr(fo, k), what=k)
 
 
 @pytest.mark.parametrize("nranks,zbc", [(2, P), (3, N)])
@@ -159,7 +160,7 @@ def test_slab_energy_rbsor_bitwise(hip_lib, monkeypatch, nranks, zbc):
     finally:
         oracle.set_projection_poisson_params(None)
     for k in fid:
-        np.testing.assert_array_equal(got[k], getattr(f, k), err_msg=k)
+        assert_bits_equal(got[k], getattr(f, k), what=k)
     assert all(t == float(np.max(f.T)) for t in tmax)
 
 

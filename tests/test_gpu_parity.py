@@ -10,6 +10,7 @@ from cfd_amd import _abi as A
 from cfd_amd import api
 from oracle import oracle
 from tests import cases
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -160,7 +161,7 @@ def test_relaxation_projection_bitwise(hip_lib, method):
     finally:
         oracle.set_projection_poisson_params(None)
     for k in ("u", "v", "w", "p"):
-        np.testing.assert_array_equal(getattr(fh, k), getattr(fo, k), err_msg=k)
+        assert_bits_equal(getattr(fh, k), getattr(fo, k), what=k)
 
 
 @pytest.mark.parametrize("shape", [(16, 16, 1), (17, 13, 11), (9, 33, 5)])
@@ -182,7 +183,7 @@ def test_device_bc_kernels_bitwise(hip_lib, shape):
             v = api.dirichlet(1.0, 2.0, 3.0, 4.0, 5.0, 6.0)
             ctx.apply_dirichlet(A.HIP_FIELD_U, v)
             oracle.bc_dirichlet(want, v)
-        np.testing.assert_array_equal(ctx.get_field(A.HIP_FIELD_U), want, err_msg=mode)
+        assert_bits_equal(ctx.get_field(A.HIP_FIELD_U), want, what=mode)
     ctx.close()
 
 
@@ -260,7 +261,7 @@ def test_poisson_relax_bitwise(hip_lib, method):
     sh, sth = ctx.poisson_solve(method, xh, rhs, g.dx, g.dy, g.dz, prm)
     assert sh == so
     assert sth.iterations == sto.iterations
-    np.testing.assert_array_equal(xh, xo)
+    assert_bits_equal(xh, xo)
     ctx.close()
 
 
@@ -307,7 +308,7 @@ def test_poisson_relax_fused_loop_bitwise(hip_lib, method, shape, kw):
         assert (sth.iterations, sth.status) == (sto.iterations, sto.status), two_pass
         assert sth.initial_residual == sto.initial_residual
         assert sth.final_residual == sto.final_residual
-        np.testing.assert_array_equal(xh, xo)
+        assert_bits_equal(xh, xo)
 
 
 def test_poisson_relax_initially_converged(hip_lib):

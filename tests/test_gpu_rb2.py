@@ -20,6 +20,7 @@ import pytest
 from cfd_amd import api
 from cfd_amd import _abi as A
 from oracle import oracle
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +68,7 @@ def test_rb2_bitwise(hip_lib, monkeypatch, shape, kw, mode, knob):
     assert (sth.iterations, sth.status) == (sto.iterations, sto.status)
     assert sth.initial_residual == sto.initial_residual
     assert sth.final_residual == sto.final_residual
-    np.testing.assert_array_equal(xh, xo)
+    assert_bits_equal(xh, xo)
 
 
 def test_rb2_stops_on_both_iterates(hip_lib, monkeypatch):
@@ -113,7 +114,7 @@ def test_rb2_tiny_front_bitwise(hip_lib, monkeypatch, mode, iters):
     assert (sth.iterations, sth.status) == (sto.iterations, sto.status)
     assert sth.initial_residual == sto.initial_residual
     assert sth.final_residual == sto.final_residual
-    np.testing.assert_array_equal(xh, xo)
+    assert_bits_equal(xh, xo)
 
 
 @pytest.mark.parametrize("iters", [5, 6])
@@ -143,6 +144,6 @@ def test_rb2_uncertified_input_bitwise(hip_lib, monkeypatch, capfd, iters):
     assert (sth.iterations, sth.status) == (sto.iterations, sto.status)
     assert sth.initial_residual == sto.initial_residual
     assert sth.final_residual == sto.final_residual
-    np.testing.assert_array_equal(xh, xo)
+    assert_bits_equal(xh, xo)
     err = capfd.readouterr().err
     assert "1 uncertified" in err, err[-2000:]

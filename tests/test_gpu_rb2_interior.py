@@ -23,6 +23,7 @@ from oracle import oracle
 from tests import cg_seam_shapes
 from tests import rb2_shapes as T
 from tests.test_gpu_rb2 import MODES
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -187,7 +188,7 @@ def test_default_layout_is_the_halved_one(hip_lib, monkeypatch, capfd, shape):
         (lay.kc, lay.tiles_x, lay.tiles_y, len(lay.runs), 0), log
     so, sto, xo = T.oracle_solve(shape, False, ("cap", 6))
     assert (s, st.iterations, st.final_residual) == (so, sto.iterations, sto.final_residual)
-    np.testing.assert_array_equal(x, xo)
+    assert_bits_equal(x, xo)
 
 
 def test_whole_step_bitwise(hip_lib, monkeypatch, capfd):

@@ -13,6 +13,7 @@ from cfd_amd import _abi as A
 from cfd_amd import api
 from oracle import oracle
 from tests import cases
+from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -125,7 +126,7 @@ def test_slab_scalar_bc_bitwise(hip_lib, nranks, bc):
         S.close()
     want = ref.copy()
     api.bc_apply_scalar_3d(want, t)
-    np.testing.assert_array_equal(got, want)
+    assert_bits_equal(got, want)
 
 
 @pytest.mark.parametrize("method,nranks", [(A.HIP_POISSON_REDBLACK, 2),
@@ -154,7 +155,7 @@ def test_slab_relaxation_projection_bitwise(hip_lib, method, nranks):
     for r in range(nranks):
         assert hist[r] == ohist, (r, hist[r], ohist)
     for k in FIELDS:
-        np.testing.assert_array_equal(got[k], getattr(f, k), err_msg=k)
+        assert_bits_equal(got[k], getattr(f, k), what=k)
 
 
 @pytest.mark.parametrize("nranks", [2, 4])
@@ -222,7 +223,7 @@ def _slab_poisson(g, rhs, nranks, method, prm=None, check_halo=False, x0=None, s
             x[glob] = xl[loc]
         if check_halo:  # halo planes hold the neighbours' final owned planes
             for c, (s, it, xl) in zip(S.ctx, res):
-                np.testing.assert_array_equal(xl, x[c.k_offset:c.k_offset + c.nz_local])
+                assert_bits_equal(xl, x[c.k_offset:c.k_offset + c.nz_local])
     finally:
         S.close()
     assert not np.isnan(x).any()
@@ -270,7 +271,7 @@ def test_slab_poisson_relax_bitwise(hip_lib, monkeypatch, method, nranks, two_pa
                                  relax_two_pass=two_pass)
     assert all(s == so for s in stat)
     assert all(i == sto.iterations for i in its)
-    np.testing.assert_array_equal(x, xo)
+    assert_bits_equal(x, xo)
 
 
 @pytest.fixture()
@@ -337,7 +338,7 @@ def test_slab8_cavity_rbsor_depth_bitwise(hip_lib, omp_oracle, monkeypatch, spli
         assert hist[r] == ohist, (r, hist[r], ohist)
     assert all(it > 10 for it, _, _ in ohist)
     for k in FIELDS:
-        np.testing.assert_array_equal(got[k], getattr(f, k), err_msg=k)
+        assert_bits_equal(got[k], getattr(f, k), what=k)
 
 
 @pytest.mark.timeout(600)
