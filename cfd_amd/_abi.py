@@ -38,12 +38,14 @@ POISSON_STAGNATED = 3
 HIP_POISSON_CG = 0
 HIP_POISSON_REDBLACK = 1
 HIP_POISSON_JACOBI = 2
+HIP_POISSON_BICGSTAB = 3  # hip_proj_poisson_solve / _ex only, not a projection-step method
 HIP_FIELD_U, HIP_FIELD_V, HIP_FIELD_W, HIP_FIELD_P, HIP_FIELD_T, HIP_FIELD_RHO = range(6)
 KERNEL_TIMERS = ["predictor", "cg_setup", "cg_sweep_a", "cg_sweep_b", "corrector",
                  "relax", "residual", "energy", "rk_stage", "cg_sweep_bx", "cc_update",
-                 "cc_spmv", "halo", "allreduce", "cg_small", "relax2", "cc_fused", "cc_fold"]
+                 "cc_spmv", "halo", "allreduce", "cg_small", "relax2", "cc_fused", "cc_fold",
+                 "bcg_v", "bcg_t", "bcg_x"]
 HIP_KT_COUNT = len(KERNEL_TIMERS)
-HIP_PROJ_ABI_VERSION = 3  # projection_hip.h
+HIP_PROJ_ABI_VERSION = 4  # projection_hip.h
 
 # oracle_poisson_kind_t
 ORACLE_POISSON_CG = 0

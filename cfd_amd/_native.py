@@ -249,6 +249,7 @@ def _bind_hip(lib) -> None:
     _sig(lib, "create_cg_gpu_solver", P(A.PoissonSolver))
     _sig(lib, "create_redblack_gpu_solver", P(A.PoissonSolver))
     _sig(lib, "create_jacobi_gpu_solver", P(A.PoissonSolver))
+    _sig(lib, "create_bicgstab_gpu_solver", P(A.PoissonSolver))
     # gpu_device.h API
     _sig(lib, "gpu_config_default", A.GpuConfig)
     _sig(lib, "gpu_is_available", C.c_int)

@@ -683,3 +683,13 @@ class HipProjection:
             self.close()
         except Exception:
             pass
+
+
+def bicgstab_gpu_solver():
+    """The poisson_solver_t* of create_bicgstab_gpu_solver (libcfd_hip.so), the
+    symbol the reference's poisson_solver_create links for BiCGSTAB on the GPU.
+    Drive it with the host library's poisson_solver_init / _solve / _destroy."""
+    s = _native.hip().create_bicgstab_gpu_solver()
+    if not s:
+        raise RuntimeError("create_bicgstab_gpu_solver: " + _native.last_error())
+    return s

@@ -120,6 +120,11 @@ struct hip_proj_ctx : TilePlan {
     std::vector<float> placement_ms;     // placement draws: ms per probe iteration, per draw
     int placement_pick = -1;             // the draw kept (-1: no draws)
     double* r2 = nullptr;                // k_ccf: r_{it+1} when r_it is in r (by parity)
+    // BiCGSTAB (bicgstab.hpp), allocated by the first such solve: the shadow
+    // residual, s and t, its state and the partials of up to three dots a launch
+    double *rhat = nullptr, *bs = nullptr, *bt = nullptr;
+    void* bcgst = nullptr;
+    double* bcg_part = nullptr;
     double* partials = nullptr;
     unsigned* counter = nullptr;
     unsigned long long* red = nullptr;   // [0] max |u|^2, [1] max |p|, [2] nonfinite, [3] max T, [4] residual

@@ -15,6 +15,7 @@
 #include <array>
 #include "rb2.hpp"
 #include "ccf.hpp"
+#include "bicgstab.hpp"
 
 template <int TY, bool FIRST, bool DIST, int FL, bool FOLD>
 static void launch_cgA_t(hip_proj_ctx* c, const Lap& L, const double* r, const double* po,
@@ -509,6 +510,121 @@ static cfd_status_t cg_solve(hip_proj_ctx* c, double dx, double dy, double dz,
     if (final_bc && neumann && !stagnated && !(s.iterations == 0 && s.status == ST_CONVERGED))
         launch_bc(c, x, 0, dv);
     ST_TRY(halo(c, {x}));
+    c->pstats.status = (poisson_solver_status_t)s.status;
+    c->pstats.iterations = s.iterations;
+    c->pstats.initial_residual = s.res0;
+    c->pstats.final_residual = s.res;
+    return (s.status == ST_CONVERGED) ? CFD_SUCCESS : CFD_ERROR_MAX_ITER;
+}
+
+// ---------------------------------------------------------------------------
+// BiCGSTAB (bicgstab.hpp): one device, rhs from c->rhs, x in c->pn. p_it and
+// v_it live in the p ring: p in pa / pb and v in pc4 / pd4, by the parity of it.
+// ---------------------------------------------------------------------------
+template <int TY>
+static void launch_bcg(hip_proj_ctx* c, const Lap& L, int it, int kt_base) {
+    BcgState* st = (BcgState*)c->bcgst;
+    const dim3 grid(sweep_grid(c)), blk(64 * TY);
+    double* pn = (it & 1) ? c->pb : c->pa;
+    double* po = (it & 1) ? c->pa : c->pb;
+    double* vn = (it & 1) ? c->pd4 : c->pc4;
+    double* vo = (it & 1) ? c->pc4 : c->pd4;
+    timed(c, kt_base, [&] {
+        if (it == 0)
+            hipExtLaunchKernelGGL((k_bcg_sweep<TY, 0, true>), grid, blk, 0, c->stream, c->ta,
+                                  c->tb, 0, c->sgeo, L, (const double*)c->r, (const double*)po,
+                                  (const double*)vo, (const double*)c->rhat, pn, vn, st,
+                                  c->bcg_part, c->counter, it);
+        else
+            hipExtLaunchKernelGGL((k_bcg_sweep<TY, 0, false>), grid, blk, 0, c->stream, c->ta,
+                                  c->tb, 0, c->sgeo, L, (const double*)c->r, (const double*)po,
+                                  (const double*)vo, (const double*)c->rhat, pn, vn, st,
+                                  c->bcg_part, c->counter, it);
+    }, it);
+    timed(c, kt_base + 1, [&] {
+        hipExtLaunchKernelGGL((k_bcg_sweep<TY, 1, false>), grid, blk, 0, c->stream, c->ta, c->tb,
+                              0, c->sgeo, L, (const double*)c->r, (const double*)vn,
+                              (const double*)nullptr, (const double*)nullptr, c->bs, c->bt, st,
+                              c->bcg_part, c->counter, it);
+    }, it);
+    timed(c, kt_base + 2, [&] {
+        hipExtLaunchKernelGGL((k_bcg_x<TY>), grid, blk, 0, c->stream, c->ta, c->tb, 0, c->sgeo,
+                              c->pn, (const double*)pn, (const double*)c->bs,
+                              (const double*)c->bt, (const double*)c->rhat, c->r, st,
+                              c->bcg_part, c->counter, it);
+    }, it);
+}
+
+static cfd_status_t bicgstab_solve(hip_proj_ctx* c, double dx, double dy, double dz,
+                                   double rel_tol, double abs_tol, int max_iter,
+                                   int check_interval) {
+    const Lap L = make_lap(dx, dy, dz);
+    const int G = tile_grid(c);
+    const DirVals dv{};
+    double* x = c->pn;
+    const size_t n = field_elems(c);
+    if (!c->rhat) ST_TRY(dalloc(c, &c->rhat, n));
+    if (!c->bs) ST_TRY(dalloc(c, &c->bs, n));
+    if (!c->bt) ST_TRY(dalloc(c, &c->bt, n));
+    if (!c->bcgst) HIP_TRY(hipMalloc(&c->bcgst, sizeof(BcgState)));
+    if (!c->bcg_part)
+        HIP_TRY(hipMalloc((void**)&c->bcg_part,
+                          sizeof(double) * (size_t)std::max(3 * sweep_grid(c), G)));
+    BcgState* st = (BcgState*)c->bcgst;
+    if (c->cg_scratch_dirty) {  // as cg_solve: zero walls of r and of the ring (p, v)
+        for (double* f : {c->r, c->pa, c->pb, c->pc4, c->pd4, c->r2})
+            if (f) HIP_TRY(hipMemsetAsync(f, 0, n * sizeof(double), c->stream));
+        c->cg_scratch_dirty = 0;
+    }
+    // poisson_solver_apply_bc(x) at solve start (linear_solver_bicgstab.c:295)
+    const bool neumann = (c->poisson_bc == HIP_POISSON_BC_NEUMANN);
+    if (neumann) launch_bc(c, x, 0, dv);
+    timed(c, HIP_KT_CG_SETUP, [&] {
+        hipExtLaunchKernelGGL(k_bcg_setup, dim3(G), dim3(NT), 0, c->stream, c->ta, c->tb, 0,
+                              c->geo, L, (const double*)c->rhs, (const double*)x, c->r, c->rhat,
+                              st, c->bcg_part, c->counter, rel_tol, abs_tol, max_iter,
+                              check_interval);
+    });
+    auto step_it = [&](int it) {
+        if (c->sweep_ty == 4) launch_bcg<4>(c, L, it, HIP_KT_BCG_V);
+        else if (c->sweep_ty == 16) launch_bcg<16>(c, L, it, HIP_KT_BCG_V);
+        else launch_bcg<8>(c, L, it, HIP_KT_BCG_V);
+    };
+    // the host polls a pinned copy of the state once per chunk, one chunk
+    // behind, as cg_solve does
+    BcgState* hs = reinterpret_cast<BcgState*>(c->h_state);  // pinned, >= 3 BcgState
+    int it = 0, chunk = 8, slot = 0, prev = -1;
+    const int chunk_max = std::max(1, c->cfg.poll_interval);
+    while (it < max_iter) {
+        const int nq = std::min(chunk, max_iter - it);
+        for (int q = 0; q < nq; ++q, ++it) step_it(it);
+        HIP_TRY(hipMemcpyAsync(&hs[slot], st, sizeof(BcgState), hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(hipEventRecord(c->ev_poll[slot], c->stream));
+        if (prev >= 0) {
+            HIP_TRY(hipEventSynchronize(c->ev_poll[prev]));
+            if (hs[prev].done) break;
+        }
+        prev = slot;
+        slot ^= 1;
+        chunk = std::min(chunk * 2, chunk_max);
+    }
+    hipExtLaunchKernelGGL(k_bcg_finalize, dim3(G), dim3(NT), 0, c->stream, c->ta, c->tb, 0,
+                          c->geo, (const double*)c->pa, (const double*)c->pb, x,
+                          (const BcgState*)st);
+    HIP_TRY(hipMemcpyAsync(&hs[2], st, sizeof(BcgState), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const BcgState s = hs[2];
+    flush_timing(c, s.iterations);
+    if (!s.done) {
+        set_err(CFD_ERROR, "projection_hip: BiCGSTAB device loop ended without a decision");
+        return CFD_ERROR;
+    }
+    // the closing poisson_solver_apply_bc (:483): every breakdown exit and the
+    // converged-at-start return leave before it
+    if (neumann && s.status != ST_STAGNATED &&
+        !(s.iterations == 0 && s.status == ST_CONVERGED && s.res0 < s.abs_tol))
+        launch_bc(c, x, 0, dv);
     c->pstats.status = (poisson_solver_status_t)s.status;
     c->pstats.iterations = s.iterations;
     c->pstats.initial_residual = s.res0;
@@ -1221,6 +1337,8 @@ static void free_ctx(hip_proj_ctx* c) {
     if (c->rxst) hipFree(c->rxst);
     if (c->rxst2) hipFree(c->rxst2);
     if (c->rb2dec) hipFree(c->rb2dec);
+    if (c->bcgst) hipFree(c->bcgst);
+    if (c->bcg_part) hipFree(c->bcg_part);
     if (c->partials) hipFree(c->partials);
     if (c->counter) hipFree(c->counter);
     if (c->red) hipFree(c->red);
@@ -2264,6 +2382,19 @@ cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* c, int method, double* x,
         set_err(CFD_ERROR_UNSUPPORTED, "hip_proj_poisson_solve_ex: caller BCs on Z-slabs");
         return CFD_ERROR_UNSUPPORTED;
     }
+    if (method == HIP_POISSON_BICGSTAB) {  // refused before anything is uploaded
+        const char* why = nullptr;
+        if (bc_mode == HIP_POISSON_BC_FIXED)
+            why = "hip_proj_poisson_solve_ex: BiCGSTAB takes BC_NEUMANN or BC_NONE, not BC_FIXED";
+        else if (dist(c))
+            why = "hip_proj_poisson_solve_ex: BiCGSTAB runs on one device, not on Z-slabs";
+        else if (c->cfg.cg_variant == 1)
+            why = "hip_proj_poisson_solve_ex: BiCGSTAB needs a cg_variant 0 context";
+        if (why) {
+            set_err(CFD_ERROR_UNSUPPORTED, why);
+            return CFD_ERROR_UNSUPPORTED;
+        }
+    }
     HIP_TRY(hipSetDevice(c->device));
     if (bc_mode == HIP_POISSON_BC_FIXED) {
         if (!c->bcfix) ST_TRY(dalloc(c, &c->bcfix, field_elems(c)));
@@ -2308,6 +2439,8 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
     if (method == HIP_POISSON_CG) {
         DivCoef dc{};
         s = cg_solve(c, dx, dy, dz, dc, RHS_FROM_ARRAY, rel, abs_tol, maxit, ci, true);
+    } else if (method == HIP_POISSON_BICGSTAB) {
+        s = bicgstab_solve(c, dx, dy, dz, rel, abs_tol, maxit, ci);
     } else {
         s = relax_solve(c, method, dx, dy, dz, rel, abs_tol, maxit, ci, omega);
     }

@@ -2,17 +2,17 @@
  * poisson_hip_plugin.c -- the poisson_solver_t GPU backend (POISSON_BACKEND_GPU).
  *
  * The reference's factories create_cg_gpu_solver / create_redblack_gpu_solver /
- * create_jacobi_gpu_solver (declared in lib/src/solvers/linear/linear_solver_internal.h:54-57,
- * reached through poisson_solver_create, linear_solver.c:150-235) under the same
- * names, so the reference's linear_solver.c links them unchanged. Like the
+ * create_jacobi_gpu_solver / create_bicgstab_gpu_solver (declared in
+ * lib/src/solvers/linear/linear_solver_internal.h:54-58, reached through
+ * poisson_solver_create, linear_solver.c:150-235) under the same names, so the reference's linear_solver.c links them unchanged. Like the
  * reference's backends (poisson_solver_cg_gpu.cu:55-203) they keep host-buffer
  * semantics: solve uploads x and rhs, runs the whole iteration in HBM, and
  * downloads x; iterate and apply_bc stay NULL.
  *
  * A caller may override solver->apply_bc (test_poisson_3d.c:274); the
  * reference's CUDA backends ignore it, these honour it:
- *  - CG applies the BC only at solve start and end (linear_solver_cg.c:320,
- *    447), so the override runs on the host around the device solve, which
+ *  - CG and BiCGSTAB apply the BC only at solve start and end
+ *    (linear_solver_cg.c:320, 447; linear_solver_bicgstab.c:295, 483), so the override runs on the host around the device solve, which
  *    then never writes boundary cells (HIP_POISSON_BC_NONE): any override;
  *  - RB-SOR / Jacobi apply it after every iteration. An override that
  *    leaves the interior alone and writes x-independent boundary values
@@ -24,9 +24,10 @@
  * Numerics follow the CPU reference the HIP kernels are pinned to (lagged-BC CG,
  * linear_solver_cg.c:290-461; RB-SOR with the odd colour first and the L-inf
  * check, linear_solver_redblack.c:80-147 + linear_solver.c:397-485; Jacobi,
- * linear_solver_jacobi.c:76-129), with the caller's poisson_solver_params_t.
- * BiCGSTAB (create_bicgstab_gpu_solver) is outside the projection path and
- * is not provided.
+ * linear_solver_jacobi.c:76-129; BiCGSTAB with its half-step exits,
+ * linear_solver_bicgstab.c:265-495), with the caller's poisson_solver_params_t.
+ * BiCGSTAB is outside the projection step: its context is created with the
+ * default configuration and the method is passed per solve.
  */
 #include "cfd_hip/projection_hip.h"
 
@@ -59,7 +60,9 @@ static cfd_status_t phip_init(poisson_solver_t* solver, size_t nx, size_t ny, si
         pc->ctx = NULL;
     }
     hip_proj_config_t cfg = hip_proj_config_default();
-    cfg.poisson_method = pc->method;
+    /* hip_proj_config_t.poisson_method is the projection step's and has no
+     * BiCGSTAB value; the solve call names the method */
+    if (pc->method != HIP_POISSON_BICGSTAB) cfg.poisson_method = pc->method;
     pc->ctx = hip_proj_create(nx, ny, nz < 1 ? 1 : nz, &cfg);
     if (!pc->ctx) {
         perr(CFD_ERROR_NOMEM, "GPU Poisson: device context creation failed");
@@ -139,10 +142,10 @@ static cfd_status_t phip_solve(poisson_solver_t* solver, double* x, double* x_te
     if (!solver->apply_bc)
         return hip_proj_poisson_solve(pc->ctx, pc->method, x, rhs, solver->dx, solver->dy, dz,
                                       &solver->params, stats);
-    if (pc->method == HIP_POISSON_CG) {
+    if (pc->method == HIP_POISSON_CG || pc->method == HIP_POISSON_BICGSTAB) {
         poisson_solver_stats_t st;
         memset(&st, 0, sizeof(st));
-        solver->apply_bc(solver, x); /* linear_solver_cg.c:320 */
+        solver->apply_bc(solver, x); /* linear_solver_cg.c:320, linear_solver_bicgstab.c:295 */
         cfd_status_t r = hip_proj_poisson_solve_ex(pc->ctx, pc->method, x, rhs, solver->dx,
                                                    solver->dy, dz, &solver->params, &st,
                                                    HIP_POISSON_BC_NONE, NULL);
@@ -210,4 +213,9 @@ poisson_solver_t* create_redblack_gpu_solver(void) {
 
 poisson_solver_t* create_jacobi_gpu_solver(void) {
     return make("jacobi_gpu", "Jacobi (HIP, MI355X)", POISSON_METHOD_JACOBI, HIP_POISSON_JACOBI);
+}
+
+poisson_solver_t* create_bicgstab_gpu_solver(void) {
+    return make("bicgstab_gpu", "BiCGSTAB (HIP, MI355X)", POISSON_METHOD_BICGSTAB,
+                HIP_POISSON_BICGSTAB);
 }

@@ -47,7 +47,11 @@ extern "C" {
 typedef enum {
     HIP_POISSON_CG = 0,       /* textbook CG, linear_solver_cg.c:290-461 */
     HIP_POISSON_REDBLACK = 1, /* Red-Black SOR, linear_solver_redblack.c:80-147 */
-    HIP_POISSON_JACOBI = 2    /* Jacobi, linear_solver_jacobi.c:76-129 */
+    HIP_POISSON_JACOBI = 2,   /* Jacobi, linear_solver_jacobi.c:76-129 */
+    /* BiCGSTAB, linear_solver_bicgstab.c:265-495. A method of
+     * hip_proj_poisson_solve / _ex only (BC_NEUMANN or BC_NONE, one device,
+     * cg_variant 0); hip_proj_config_t.poisson_method does not take it. */
+    HIP_POISSON_BICGSTAB = 3
 } hip_poisson_method_t;
 
 /* Device/solver configuration (role of gpu_config_t, gpu_device.h:32-53). The
@@ -157,7 +161,10 @@ typedef enum {
     HIP_KT_CC_FUSED = 16,  /* cg_variant 1: the whole iteration in one z-march (k_ccf, one
                               device, 3-D); the first and the plain launches (version 3) */
     HIP_KT_CC_FOLD = 17,   /* cg_variant 1: the k_ccf launches that also fold x (every 4th) */
-    HIP_KT_COUNT = 18
+    HIP_KT_BCG_V = 18,     /* BiCGSTAB: p = r + beta (p - omega v), v = A p, (r^, v) */
+    HIP_KT_BCG_T = 19,     /* BiCGSTAB: s = r - alpha v, t = A s, (s,s), (t,s), (t,t) */
+    HIP_KT_BCG_X = 20,     /* BiCGSTAB: x += alpha p + omega s, r = s - omega t, (r,r), (r^,r) */
+    HIP_KT_COUNT = 21
 } hip_kernel_timer_t;
 
 CFD_HIP_EXPORT hip_proj_config_t hip_proj_config_default(void);
@@ -261,8 +268,10 @@ CFD_HIP_EXPORT int hip_proj_get_placement(hip_proj_ctx_t* ctx, double* ms_per_it
  * hip_proj_get_timing_n, projection_hip_cg1. Version 3: HIP_KT_COUNT 18
  * (HIP_KT_CC_FOLD split from HIP_KT_CC_FUSED), hip_proj_get_clock_sample,
  * hip_proj_get_placement, hip_proj_comm_mailbox_bench; the legacy getter
- * writes 17 entries. */
-#define HIP_PROJ_ABI_VERSION 3
+ * writes 17 entries. Version 4: HIP_POISSON_BICGSTAB,
+ * create_bicgstab_gpu_solver, HIP_KT_COUNT 21 (HIP_KT_BCG_V / _T / _X
+ * appended); the legacy getter still writes 17 entries. */
+#define HIP_PROJ_ABI_VERSION 4
 CFD_HIP_EXPORT int hip_proj_abi_version(void);
 /* sha256 prefix (16 hex digits) of the sources the library was built from
  * (cfd_amd/_sha.py: csrc/hip, csrc/host, include/cfd_hip), embedded at
@@ -485,6 +494,7 @@ CFD_HIP_EXPORT ns_solver_t* create_rk4_hip_solver(void);
 CFD_HIP_EXPORT poisson_solver_t* create_cg_gpu_solver(void);
 CFD_HIP_EXPORT poisson_solver_t* create_redblack_gpu_solver(void);
 CFD_HIP_EXPORT poisson_solver_t* create_jacobi_gpu_solver(void);
+CFD_HIP_EXPORT poisson_solver_t* create_bicgstab_gpu_solver(void);
 /* Registers the five names above through cfd_registry_register(). */
 CFD_HIP_EXPORT void cfd_hip_register_solvers(ns_solver_registry_t* registry);
 
