@@ -6,9 +6,15 @@ the Makefile embeds it in the library as hip_proj_build_id() and
 cfd_amd._native refuses a library whose id differs from the sources beside it.
 `kernel_source_sha()` hashes the HIP sources only, and `device_code_sha(lib)`
 the device code inside a built library: PMC profiles are keyed on both
-(their byte counts depend on the kernels, not on host code; the HIP sources
-also hold host code, so a host-only edit changes the first key, not the
-second).
+(their byte counts depend on the kernels, not on host code). The HIP sources
+also hold host code, so a host-only edit changes the first key. It leaves the
+second unchanged only while it keeps the order in which the host code first
+refers to each kernel instantiation: the compiler lays the kernels out in
+that order, so moving a host function, or reordering the branches that pick
+a template argument, moves the kernels inside .text and with them
+`device_code_sha`, though every kernel's bytes stay the same.
+tools/device_symbols.py compares two libraries kernel by kernel (name, size,
+hash of the bytes) for that case.
 
 Standard library only: the Makefile runs this file as a script
 (`python3 _sha.py` prints the library sha).
@@ -76,10 +82,11 @@ def _offload_bundles(fb: bytes):
 def device_code_sha(lib) -> str | None:
     """sha256[:16] of the gfx950 device code inside a built library: the
     .text and .rodata (instructions and kernel descriptors) of every code
-    object in its .hip_fatbin. Host-only source edits and the build
-    directory (which enters the per-file compilation id, hence the code
-    objects' symbols) leave it unchanged; any kernel change alters it. None
-    for a file without gfx950 code."""
+    object in its .hip_fatbin. The build directory (which enters the
+    per-file compilation id, hence the code objects' symbols) and host-only
+    source edits that keep the kernels' order (module docstring) leave it
+    unchanged; any kernel change alters it. None for a file without gfx950
+    code."""
     data = Path(lib).read_bytes()
     if data[:4] != b"\x7fELF" or data[4] != 2 or data[5] != 1:
         return None

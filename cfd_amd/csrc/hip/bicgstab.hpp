@@ -55,7 +55,6 @@ struct BcgState {
     int max_iter;
     int check_interval;
 };
-static_assert(sizeof(BcgState) <= sizeof(CgState), "BcgState polls through the CgState slots");
 
 constexpr double BCG_BREAKDOWN = 1e-30;  // BICGSTAB_BREAKDOWN_THRESHOLD
 

@@ -1,6 +1,7 @@
 // ctx.hpp -- the device context behind the hip_proj_* C-ABI and the helpers
-// shared by its translation units (projection_hip.hip: projection step and
-// Poisson solvers; rk4_hip.hip: the RK4 integrator). Private to the library.
+// shared by its translation units (projection_hip.hip: projection step, with
+// the Poisson solvers of poisson_solve.hpp; rk4_hip.hip: the RK4 integrator).
+// Private to the library.
 #pragma once
 
 #include "kernels.hpp"
@@ -20,6 +21,11 @@
 #include <vector>
 
 using namespace cfdhip;
+
+namespace cfdhip {
+struct Rb2Dec;    // rb2.hpp
+struct BcgState;  // bicgstab.hpp
+}  // namespace cfdhip
 
 // Error reporting goes through the host library's thread-local error state
 // (cfd_set_error, logging.c:39-46 in the reference). Weak, so the library
@@ -48,6 +54,13 @@ struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
     int iter;  // CG iteration of a sweep launch, -1 otherwise
+};
+
+// One pinned slot of the polled device loop (poisson_solve.hpp): raw storage
+// for a copy of whichever state struct the solver in progress keeps on the
+// device (CgState, RxState, BcgState)
+struct alignas(16) PollSlot {
+    unsigned char bytes[128];
 };
 
 }  // namespace
@@ -116,19 +129,19 @@ struct hip_proj_ctx : TilePlan {
     CgState* st = nullptr;
     RxState* rxst = nullptr;             // fused relaxation loop state
     RxState* rxst2 = nullptr;            // scratch state of k_rb2's recompute sweeps
-    void* rb2dec = nullptr;              // k_rb2's decision constants (Rb2Dec, rb2.hpp)
+    Rb2Dec* rb2dec = nullptr;            // k_rb2's decision constants (rb2.hpp)
     std::vector<float> placement_ms;     // placement draws: ms per probe iteration, per draw
     int placement_pick = -1;             // the draw kept (-1: no draws)
     double* r2 = nullptr;                // k_ccf: r_{it+1} when r_it is in r (by parity)
     // BiCGSTAB (bicgstab.hpp), allocated by the first such solve: the shadow
     // residual, s and t, its state and the partials of up to three dots a launch
     double *rhat = nullptr, *bs = nullptr, *bt = nullptr;
-    void* bcgst = nullptr;
+    BcgState* bcgst = nullptr;
     double* bcg_part = nullptr;
     double* partials = nullptr;
     unsigned* counter = nullptr;
     unsigned long long* red = nullptr;   // [0] max |u|^2, [1] max |p|, [2] nonfinite, [3] max T, [4] residual
-    CgState* h_state = nullptr;          // pinned, 2 slots + final
+    PollSlot* h_state = nullptr;         // pinned, 2 slots + final
     unsigned long long* h_red = nullptr; // pinned, 8
     hipEvent_t ev_poll[2] = {nullptr, nullptr};
     double rho0 = 1.0;
@@ -276,9 +289,45 @@ static unsigned shell_blocks(const hip_proj_ctx* c) {
     return (unsigned)std::max(1LL, std::min(b, 65535LL));
 }
 
+// Every kernel launch of the context: hipExtLaunchKernelGGL on stream `s`
+// with the (ta, tb) of the launch being timed (see timed() above). The
+// arguments convert to the kernel's own parameter types K..., so nullptr and
+// double* -> const double* need no cast.
+template <class T>
+struct ident_t {
+    using type = T;
+};
+
+template <class... K>
+static void klaunch_on(hip_proj_ctx* c, hipStream_t s, void (*k)(K...), dim3 grid, dim3 block,
+                       typename ident_t<K>::type... a) {
+    hipExtLaunchKernelGGL(k, grid, block, 0, s, c->ta, c->tb, 0, a...);
+}
+
+// ... on the context's stream
+template <class... K>
+static void klaunch(hip_proj_ctx* c, void (*k)(K...), dim3 grid, dim3 block,
+                    typename ident_t<K>::type... a) {
+    klaunch_on(c, c->stream, k, grid, block, a...);
+}
+
+// A runtime switch as a template argument: f(BoolC<b>{}), or f(IntC<v>{}) for
+// the v among V0, Vs... (any other v: V0). f is instantiated for the listed
+// values only, true before false and in the order Vs..., V0: the kernels it
+// names land in the code object in that order (cfd_amd/_sha.py).
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(BoolC<true>{});
+    else f(BoolC<false>{});
+}
+
+template <int V0, int... Vs, class F>
+static void with_int(int v, F&& f) {
+    if (!(... || (v == Vs && (f(IntC<Vs>{}), true)))) f(IntC<V0>{});
+}
+
 static void launch_bc(hip_proj_ctx* c, double* f, int mode, const DirVals& dv) {
-    hipExtLaunchKernelGGL(k_bc_shell, dim3(shell_blocks(c)), dim3(256), 0, c->stream, c->ta, c->tb, 0, c->geo, f,
-                       mode, dv);
+    klaunch(c, k_bc_shell, dim3(shell_blocks(c)), dim3(256), c->geo, f, mode, dv);
 }
 
 static __global__ void k_init_red(unsigned long long* red) {

@@ -42,30 +42,18 @@ static cfd_status_t ensure_rk(hip_proj_ctx* c, bool stages) {
 template <int S>
 static void launch_stage(hip_proj_ctx* c, bool buoy, const RkCoef& rc, const Fld4& cur,
                          const Fld4& q0, const Fld4& acc, const Fld4& out) {
+    auto go = [&](auto kern, dim3 grid) {
+        klaunch(c, kern, grid, dim3(256), c->geo, rc, cur, q0, acc, out, c->rho, c->T, c->dxa,
+                c->dya, c->src_u_row, c->src_v_col);
+    };
     // x-pair stage kernel (default); CFD_HIP_RK_PAIR=0 selects the per-cell one
-    const bool pair = c->env.rk_pair;
-    if (pair) {
+    if (c->env.rk_pair) {
         const dim3 g2((unsigned)((c->nx + 127) / 128), (unsigned)((c->ny + 3) / 4),
                       (unsigned)c->nz);
-        if (buoy)
-            hipExtLaunchKernelGGL((k_rk_stage2<S, true>), g2, dim3(256), 0, c->stream, c->ta,
-                                  c->tb, 0, c->geo, rc, cur, q0, acc, out, c->rho, c->T, c->dxa,
-                                  c->dya, c->src_u_row, c->src_v_col);
-        else
-            hipExtLaunchKernelGGL((k_rk_stage2<S, false>), g2, dim3(256), 0, c->stream, c->ta,
-                                  c->tb, 0, c->geo, rc, cur, q0, acc, out, c->rho, c->T, c->dxa,
-                                  c->dya, c->src_u_row, c->src_v_col);
-        return;
+        with_bool(buoy, [&](auto B) { go(k_rk_stage2<S, B>, g2); });
+    } else {
+        with_bool(buoy, [&](auto B) { go(k_rk_stage<S, B>, cell_grid(c)); });
     }
-    const dim3 grid = cell_grid(c);
-    if (buoy)
-        hipExtLaunchKernelGGL((k_rk_stage<S, true>), grid, dim3(256), 0, c->stream, c->ta, c->tb,
-                              0, c->geo, rc, cur, q0, acc, out, c->rho, c->T, c->dxa, c->dya,
-                              c->src_u_row, c->src_v_col);
-    else
-        hipExtLaunchKernelGGL((k_rk_stage<S, false>), grid, dim3(256), 0, c->stream, c->ta,
-                              c->tb, 0, c->geo, rc, cur, q0, acc, out, c->rho, c->T, c->dxa,
-                              c->dya, c->src_u_row, c->src_v_col);
 }
 
 static cfd_status_t step_tail(hip_proj_ctx* c, const grid* g, const ns_solver_params_t* prm,
@@ -269,14 +257,8 @@ static cfd_status_t euler_step_impl(hip_proj_ctx* c, const grid* g, const ns_sol
     const Fld4 out{{c->us, c->vs, c->ws, c->pn}};
     const dim3 g2((unsigned)((c->nx + 127) / 128), (unsigned)((c->ny + 3) / 4), (unsigned)c->nz);
     timed(c, HIP_KT_RK_STAGE, [&] {
-        if (buoy)
-            hipExtLaunchKernelGGL((k_euler_step<true>), g2, dim3(256), 0, c->stream, c->ta, c->tb,
-                                  0, c->geo, rc, cur, out, c->rho, c->T, c->dxa, c->dya,
-                                  c->src_u_row, c->src_v_col);
-        else
-            hipExtLaunchKernelGGL((k_euler_step<false>), g2, dim3(256), 0, c->stream, c->ta,
-                                  c->tb, 0, c->geo, rc, cur, out, c->rho, c->T, c->dxa, c->dya,
-                                  c->src_u_row, c->src_v_col);
+        klaunch(c, buoy ? k_euler_step<true> : k_euler_step<false>, g2, dim3(256), c->geo, rc, cur,
+                out, c->rho, c->T, c->dxa, c->dya, c->src_u_row, c->src_v_col);
     });
     HIP_TRY(hipGetLastError());
     std::swap(c->u, c->us);

@@ -20,7 +20,7 @@ is_interior() to the product's planner without a GPU:
       groups of four with the per-plane tests (ZB) up to step n_s, steady
       groups of four (ZB = false) while n + 3 < n_e, ZB groups of four to the
       end and up to three single steps
-  projection_hip.hip, relax_solve_rb2
+  poisson_solve.hpp, relax_solve_rb2 (poll_loop)
       the chunked launch loop (8 iterates, doubling to poll_interval, the
       decision read one chunk behind)
 The box is 1.0 x 0.7 x 1.3: dx, dy and dz all differ and all are below 1, so
