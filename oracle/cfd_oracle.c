@@ -812,7 +812,7 @@ double oracle_max_temperature(const flow_field* f) {
 }
 
 /* ------------------------------------------------------------------------ */
-/* projection step (solver_projection.c:46-297, max_iter = 1)                */
+/* projection (solver_projection.c:46-297): one step, and the max_iter loop   */
 /* ------------------------------------------------------------------------ */
 
 /* boundary_copy_utils.h:93-148 */
@@ -850,9 +850,11 @@ static void copy_boundary_velocities_3d(double* du, double* dv, double* dw, cons
 
 static inline double clampv(double x) { return fmax(-MAX_VELOCITY, fmin(MAX_VELOCITY, x)); }
 
-cfd_status_t oracle_projection_step(flow_field* field, const grid* grid,
-                                    const ns_solver_params_t* params, ns_solver_stats_t* stats,
-                                    oracle_poisson_kind_t pkind, int* poisson_iters) {
+/* one pass of the loop body of solver_projection.c:111-290 at step index iter */
+static cfd_status_t projection_iteration(flow_field* field, const grid* grid,
+                                         const ns_solver_params_t* params,
+                                         ns_solver_stats_t* stats, oracle_poisson_kind_t pkind,
+                                         int* poisson_iters, const int iter) {
     if (!field || !grid || !params) return CFD_ERROR_INVALID;
     if (field->nx < 3 || field->ny < 3 || (field->nz > 1 && field->nz < 3)) return CFD_ERROR_INVALID;
     size_t nx = field->nx, ny = field->ny, nz = field->nz;
@@ -881,7 +883,6 @@ cfd_status_t oracle_projection_step(flow_field* field, const grid* grid,
     memcpy(pn, field->p, bytes);
 
     double t0 = now_ms();
-    const int iter = 0; /* projection_step forces max_iter = 1 (solver_registry.c:928-929) */
     const double* U = field->u;
     const double* V = field->v;
     const double* W = field->w;
@@ -1023,6 +1024,34 @@ cfd_status_t oracle_projection_step(flow_field* field, const grid* grid,
 done:
     free(us); free(vs); free(ws); free(pn); free(pt); free(rhs);
     return st;
+}
+
+/* projection_step forces max_iter = 1 (solver_registry.c:928-929): step index 0 */
+cfd_status_t oracle_projection_step(flow_field* field, const grid* grid,
+                                    const ns_solver_params_t* params, ns_solver_stats_t* stats,
+                                    oracle_poisson_kind_t pkind, int* poisson_iters) {
+    return projection_iteration(field, grid, params, stats, pkind, poisson_iters, 0);
+}
+
+/* The loop of solver_projection.c:111-290. Its work arrays outlive an
+ * iteration there, but each is rewritten in full before it is read: u*, v*,
+ * w* by the predictor and copy_boundary_velocities_3d, rhs by the divergence
+ * loop, and p_new equals field->p after :253. So n passes of the body are
+ * the loop, with iter in the source terms and the energy step's time. */
+cfd_status_t oracle_projection_solve(flow_field* field, const grid* grid,
+                                     const ns_solver_params_t* params, ns_solver_stats_t* stats,
+                                     oracle_poisson_kind_t pkind, int n_steps,
+                                     int* poisson_iters) {
+    if (!field || !grid || !params) return CFD_ERROR_INVALID;
+    if (field->nx < 3 || field->ny < 3 || (field->nz > 1 && field->nz < 3)) return CFD_ERROR_INVALID;
+    for (int iter = 0; iter < n_steps; iter++) {
+        cfd_status_t st = projection_iteration(field, grid, params, stats, pkind,
+                                               poisson_iters ? poisson_iters + iter : NULL, iter);
+        if (st != CFD_SUCCESS) return st;
+    }
+    /* projection_solve (solver_registry.c:949-972): iterations = max_iter */
+    if (stats && n_steps > 0) stats->iterations = n_steps;
+    return CFD_SUCCESS;
 }
 
 /* ------------------------------------------------------------------------ */

@@ -13,6 +13,9 @@
  * (tests/solvers/navier_stokes/cpu/test_ns_solver_3d.c:345-348, reproduced
  * bit-exactly) and by reference outputs recorded in SURVEY.md App. B
  * (CG iteration counts, Taylor-Green L2 errors, Ghia RMS). See DESIGN.md.
+ * The RK4 step and the projection loop are also held bit for bit to records
+ * of the reference's own rk4_impl and solve_projection_method
+ * (tests/golden/make_rk_golden.py, make_projection_golden.py).
  *
  * Every function cites the reference file:line it restates.
  */
@@ -103,6 +106,17 @@ typedef enum {
 cfd_status_t oracle_projection_step(flow_field* field, const grid* g,
                                     const ns_solver_params_t* params, ns_solver_stats_t* stats,
                                     oracle_poisson_kind_t poisson, int* poisson_iters);
+
+/* projection_solve (solver_registry.c:949-972) -> solve_projection_method
+ * with max_iter = n_steps: the loop of solver_projection.c:111-290, whose
+ * index iter = 0 .. n_steps - 1 enters the source terms (exp(-decay iter dt))
+ * and the energy step's time. oracle_projection_step is its n_steps = 1 case.
+ * stats->iterations = n_steps; poisson_iters (optional, n_steps entries)
+ * receives every step's pressure-solver iteration count. */
+cfd_status_t oracle_projection_solve(flow_field* field, const grid* g,
+                                     const ns_solver_params_t* params, ns_solver_stats_t* stats,
+                                     oracle_poisson_kind_t poisson, int n_steps,
+                                     int* poisson_iters);
 
 /* Phase timings (ms) of the most recent oracle_projection_step, for the CPU
  * baseline: [0] predictor, [1] divergence, [2] poisson, [3] corrector+rest. */

@@ -53,6 +53,8 @@ def lib():
         sig("oracle_set_poisson_bc_hook", None, BC_HOOK, C.c_void_p)
         sig("oracle_projection_step", C.c_int, P(A.FlowField), P(A.Grid), P(A.SolverParams),
             P(A.SolverStats), C.c_int, P(C.c_int))
+        sig("oracle_projection_solve", C.c_int, P(A.FlowField), P(A.Grid), P(A.SolverParams),
+            P(A.SolverStats), C.c_int, C.c_int, P(C.c_int))
         sig("oracle_last_phase_ms", None, d)
         sig("oracle_last_poisson_stats", None, P(A.PoissonStats))
         sig("oracle_cg_solve", C.c_int, d, d, sz, sz, sz, C.c_double, C.c_double, C.c_double,
@@ -102,6 +104,17 @@ def projection_step(field, grid, params, poisson=A.ORACLE_POISSON_CG):
     s = lib().oracle_projection_step(field.ptr, grid.ptr, C.byref(params), C.byref(st),
                                      poisson, C.byref(it))
     return s, st, it.value
+
+
+def projection_solve(field, grid, params, n_steps, poisson=A.ORACLE_POISSON_CG):
+    """The reference's `projection` solve with max_iter = n_steps: step index
+    0 .. n_steps - 1 in the source terms. Returns (status, stats, [pressure-
+    solver iterations per step])."""
+    st = A.SolverStats()
+    its = (C.c_int * max(n_steps, 1))()
+    s = lib().oracle_projection_solve(field.ptr, grid.ptr, C.byref(params), C.byref(st),
+                                      poisson, n_steps, its)
+    return s, st, list(its)[:n_steps]
 
 
 def last_poisson_stats() -> A.PoissonStats:
