@@ -134,6 +134,28 @@ class PoissonStats(C.Structure):
                 ("elapsed_time_ms", C.c_double)]
 
 
+# field_stats / derived_fields (derived_fields.h:18-52), profile_direction
+# (csv_output.h:63-66)
+class FieldStats(C.Structure):
+    _fields_ = [("min_val", C.c_double), ("max_val", C.c_double), ("avg_val", C.c_double),
+                ("sum_val", C.c_double)]
+
+
+STAT_NAMES = ("u", "v", "w", "p", "rho", "T", "vel_mag")
+
+
+class DerivedFields(C.Structure):
+    _fields_ = [("velocity_magnitude", c_double_p),
+                ("nx", C.c_size_t), ("ny", C.c_size_t), ("nz", C.c_size_t),
+                ("u_stats", FieldStats), ("v_stats", FieldStats), ("w_stats", FieldStats),
+                ("p_stats", FieldStats), ("rho_stats", FieldStats), ("T_stats", FieldStats),
+                ("vel_mag_stats", FieldStats), ("stats_computed", C.c_int)]
+
+
+PROFILE_HORIZONTAL = 0
+PROFILE_VERTICAL = 1
+
+
 class HipProjConfig(C.Structure):
     _fields_ = [
         ("device", C.c_int), ("poisson_method", C.c_int),

@@ -141,6 +141,19 @@ def _bind_host(lib) -> None:
          C.c_double, C.c_double, C.c_double, C.c_double)
     _sig(lib, "write_vtk_flow_field", None, C.c_char_p, P(A.FlowField), C.c_size_t, C.c_size_t,
          C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double)
+    _sig(lib, "calculate_field_statistics", A.FieldStats, A.c_double_p, C.c_size_t)
+    _sig(lib, "derived_fields_create", P(A.DerivedFields), C.c_size_t, C.c_size_t, C.c_size_t)
+    _sig(lib, "derived_fields_destroy", None, P(A.DerivedFields))
+    _sig(lib, "derived_fields_clear", None, P(A.DerivedFields))
+    _sig(lib, "derived_fields_compute_velocity_magnitude", None, P(A.DerivedFields),
+         P(A.FlowField))
+    _sig(lib, "derived_fields_compute_statistics", None, P(A.DerivedFields), P(A.FlowField))
+    _sig(lib, "write_csv_timeseries", None, C.c_char_p, C.c_int, C.c_double, P(A.FlowField),
+         P(A.DerivedFields), P(A.SolverParams), P(A.SolverStats), C.c_size_t, C.c_size_t, C.c_int)
+    _sig(lib, "write_csv_centerline", None, C.c_char_p, P(A.FlowField), P(A.DerivedFields),
+         A.c_double_p, A.c_double_p, C.c_size_t, C.c_size_t, C.c_int)
+    _sig(lib, "write_csv_statistics", None, C.c_char_p, C.c_int, C.c_double, P(A.FlowField),
+         P(A.DerivedFields), C.c_size_t, C.c_size_t, C.c_int)
     _sig(lib, "poisson_solver_params_default", A.PoissonParams)
     _sig(lib, "poisson_solver_stats_default", A.PoissonStats)
     _sig(lib, "poisson_solver_backend_available", C.c_bool, C.c_int)
@@ -235,6 +248,15 @@ def _bind_hip(lib) -> None:
     _sig(lib, "create_rk4_hip_solver", P(A.NSSolver))
     _sig(lib, "cfd_hip_register_solvers", None, V)
     _sig(lib, "hip_proj_write_vtk", C.c_int, V, C.c_char_p, P(A.Grid), C.c_double)
+    _sig(lib, "hip_proj_field_statistics", C.c_int, V, C.c_int, P(A.FieldStats))
+    _sig(lib, "hip_proj_derived_statistics", C.c_int, V, C.c_int, C.c_double, P(A.DerivedFields))
+    _sig(lib, "hip_proj_velocity_magnitude", C.c_int, V, A.c_double_p)
+    _sig(lib, "hip_proj_write_csv_timeseries", C.c_int, V, C.c_char_p, C.c_int, C.c_double,
+         P(A.SolverParams), P(A.SolverStats), C.c_int, C.c_int)
+    _sig(lib, "hip_proj_write_csv_statistics", C.c_int, V, C.c_char_p, C.c_int, C.c_double,
+         C.c_double, C.c_int, C.c_int)
+    _sig(lib, "hip_proj_write_csv_centerline", C.c_int, V, C.c_char_p, P(A.Grid), C.c_int,
+         C.c_double, C.c_int)
     # boundary_conditions_gpu.h (device pointers, packed layout, opaque stream)
     _sig(lib, "bc_apply_neumann_gpu", None, V, C.c_size_t, C.c_size_t, V)
     _sig(lib, "bc_apply_scalar_gpu", None, V, C.c_size_t, C.c_size_t, C.c_int, V)

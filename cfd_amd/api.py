@@ -238,6 +238,83 @@ def checkpoint_read(path: str, caps=(128, 256, 512)):
             *[b.value.decode() if b is not None else None for b in bufs])
 
 
+def stats_dict(s: A.FieldStats) -> dict:
+    return {"min": s.min_val, "max": s.max_val, "avg": s.avg_val, "sum": s.sum_val}
+
+
+def calculate_field_statistics(data: np.ndarray) -> A.FieldStats:
+    """calculate_field_statistics (derived_fields.c:65-140), the sequential loop."""
+    a = np.ascontiguousarray(data, dtype=np.float64)
+    return _native.host().calculate_field_statistics(a.ctypes.data_as(A.c_double_p), a.size)
+
+
+class DerivedFields:
+    """derived_fields_create / _compute_velocity_magnitude / _compute_statistics /
+    _clear / _destroy of the host mirror (derived_fields.c:27-224)."""
+
+    def __init__(self, nx, ny, nz=1):
+        self._ptr = _native.host().derived_fields_create(nx, ny, nz)
+        if not self._ptr:
+            raise MemoryError("derived_fields_create")
+
+    @property
+    def ptr(self):
+        return self._ptr
+
+    @property
+    def c(self) -> A.DerivedFields:
+        return self._ptr.contents
+
+    def compute_velocity_magnitude(self, field: FlowField) -> None:
+        _native.host().derived_fields_compute_velocity_magnitude(self._ptr, field.ptr)
+
+    def compute_statistics(self, field: FlowField) -> None:
+        _native.host().derived_fields_compute_statistics(self._ptr, field.ptr)
+
+    def clear(self) -> None:
+        _native.host().derived_fields_clear(self._ptr)
+
+    @property
+    def velocity_magnitude(self) -> Optional[np.ndarray]:
+        c = self.c
+        if not c.velocity_magnitude:
+            return None
+        return _view(c.velocity_magnitude, c.nx * c.ny * c.nz, (c.nz, c.ny, c.nx))
+
+    def stats(self) -> dict:
+        return {n: stats_dict(getattr(self.c, n + "_stats")) for n in A.STAT_NAMES}
+
+    def __del__(self):
+        try:
+            if getattr(self, "_ptr", None):
+                _native.host().derived_fields_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+
+def write_csv_timeseries(path: str, step: int, time: float, field: FlowField,
+                         derived: DerivedFields, params: A.SolverParams, stats: A.SolverStats,
+                         create_new: bool) -> None:
+    nz, ny, nx = field.shape
+    _native.host().write_csv_timeseries(path.encode(), step, time, field.ptr, derived.ptr,
+                                        C.byref(params), C.byref(stats), nx, ny, int(create_new))
+
+
+def write_csv_statistics(path: str, step: int, time: float, field: FlowField,
+                         derived: DerivedFields, create_new: bool) -> None:
+    nz, ny, nx = field.shape
+    _native.host().write_csv_statistics(path.encode(), step, time, field.ptr, derived.ptr, nx, ny,
+                                        int(create_new))
+
+
+def write_csv_centerline(path: str, field: FlowField, derived: Optional[DerivedFields],
+                         grid: Grid, direction: int) -> None:
+    _native.host().write_csv_centerline(path.encode(), field.ptr,
+                                        derived.ptr if derived is not None else None,
+                                        grid.c.x, grid.c.y, grid.nx, grid.ny, direction)
+
+
 class Registry:
     """cfd_registry_create + cfd_registry_register_defaults."""
 
@@ -587,6 +664,47 @@ class HipProjection:
         _check(self._lib().hip_proj_get_field(self._ctx, fid, out.ctypes.data_as(A.c_double_p)),
                "hip_proj_get_field")
         return out
+
+    def field_statistics(self, fid: int) -> A.FieldStats:
+        """hip_proj_field_statistics: min / max / avg / sum of one resident
+        field, reduced on the GPU."""
+        s = A.FieldStats()
+        _check(self._lib().hip_proj_field_statistics(self._ctx, fid, C.byref(s)),
+               "hip_proj_field_statistics")
+        return s
+
+    def derived_statistics(self, with_vel_mag: bool = True, rho0: float = 1.0) -> A.DerivedFields:
+        """hip_proj_derived_statistics: the statistics of u, v, w, p, rho, T
+        (and of the velocity magnitude) in one fused device pass."""
+        d = A.DerivedFields()
+        d.nx, d.ny, d.nz = self.shape[2], self.shape[1], self.shape[0]
+        _check(self._lib().hip_proj_derived_statistics(self._ctx, int(with_vel_mag), rho0,
+                                                       C.byref(d)), "hip_proj_derived_statistics")
+        return d
+
+    def velocity_magnitude(self) -> np.ndarray:
+        """hip_proj_velocity_magnitude: sqrt((u*u) + (v*v) + (w*w)), packed."""
+        out = np.empty(self.shape, dtype=np.float64)
+        _check(self._lib().hip_proj_velocity_magnitude(self._ctx,
+                                                       out.ctypes.data_as(A.c_double_p)),
+               "hip_proj_velocity_magnitude")
+        return out
+
+    def write_csv_timeseries(self, path: str, step: int, time: float, params: A.SolverParams,
+                             stats: A.SolverStats, with_vel_mag: bool, create_new: bool) -> int:
+        return self._lib().hip_proj_write_csv_timeseries(
+            self._ctx, path.encode(), step, time, C.byref(params), C.byref(stats),
+            int(with_vel_mag), int(create_new))
+
+    def write_csv_statistics(self, path: str, step: int, time: float, rho0: float,
+                             with_vel_mag: bool, create_new: bool) -> int:
+        return self._lib().hip_proj_write_csv_statistics(
+            self._ctx, path.encode(), step, time, rho0, int(with_vel_mag), int(create_new))
+
+    def write_csv_centerline(self, path: str, grid: Grid, direction: int, rho0: float,
+                             with_vel_mag: bool) -> int:
+        return self._lib().hip_proj_write_csv_centerline(
+            self._ctx, path.encode(), grid.ptr, direction, rho0, int(with_vel_mag))
 
     def fill(self, fid: int, value: float):
         _check(self._lib().hip_proj_fill_field(self._ctx, fid, value), "hip_proj_fill_field")

@@ -138,6 +138,11 @@ struct hip_proj_ctx : TilePlan {
     double *rhat = nullptr, *bs = nullptr, *bt = nullptr;
     BcgState* bcgst = nullptr;
     double* bcg_part = nullptr;
+    // monitoring (derived_stats.hip), allocated by the first such call: the
+    // statistics pass's workgroup records, totals and ticket; the velocity
+    // magnitude in the padded layout
+    double* dstat = nullptr;
+    double* vmag = nullptr;
     double* partials = nullptr;
     unsigned* counter = nullptr;
     unsigned long long* red = nullptr;   // [0] max |u|^2, [1] max |p|, [2] nonfinite, [3] max T, [4] residual

@@ -22,6 +22,9 @@
  *   ns_solver_stats_t        lib/include/cfd/solvers/navier_stokes_solver.h:198-207
  *   struct NSSolver          lib/include/cfd/solvers/navier_stokes_solver.h:254-277
  *   poisson_solver_*         lib/include/cfd/solvers/poisson_solver.h:60-233
+ *   field_stats              lib/include/cfd/core/derived_fields.h:18-23
+ *   derived_fields           lib/include/cfd/core/derived_fields.h:36-52
+ *   profile_direction        lib/include/cfd/io/csv_output.h:63-66
  */
 #ifndef CFD_HIP_CFD_ABI_H
 #define CFD_HIP_CFD_ABI_H
@@ -45,6 +48,8 @@ extern "C" {
 #include "cfd/boundary/boundary_conditions.h"
 #include "cfd/solvers/navier_stokes_solver.h"
 #include "cfd/solvers/poisson_solver.h"
+#include "cfd/core/derived_fields.h"
+#include "cfd/io/csv_output.h"
 #else
 
 /* ---- status codes (values are part of the ABI) ------------------------- */
@@ -322,6 +327,34 @@ struct poisson_solver {
     poisson_solver_iterate_func iterate;
     poisson_solver_apply_bc_func apply_bc;
 };
+
+/* ---- field statistics and derived fields (monitoring / CSV outputs) ------ */
+typedef struct {
+    double min_val;
+    double max_val;
+    double avg_val;
+    double sum_val;
+} field_stats;
+
+typedef struct {
+    double* velocity_magnitude; /* sqrt(u^2 + v^2 + w^2), NULL if not computed */
+    size_t nx;
+    size_t ny;
+    size_t nz; /* 1 for 2D */
+    field_stats u_stats;
+    field_stats v_stats;
+    field_stats w_stats;
+    field_stats p_stats;
+    field_stats rho_stats;
+    field_stats T_stats;
+    field_stats vel_mag_stats;
+    int stats_computed;
+} derived_fields;
+
+typedef enum {
+    PROFILE_HORIZONTAL, /* along x at j = ny/2 */
+    PROFILE_VERTICAL    /* along y at i = nx/2 */
+} profile_direction;
 
 #endif /* CFD_HIP_REFERENCE_TYPES */
 

@@ -165,6 +165,36 @@ CFD_HIP_EXPORT void write_vtk_flow_field(const char* filename, const flow_field*
                                          double xmax, double ymin, double ymax, double zmin,
                                          double zmax);
 
+/* ---- monitoring: field statistics, velocity magnitude (derived_fields.h:18-71,
+ * derived_fields.c:27-224) and the CSV outputs built on them (csv_output.h,
+ * csv_output.c:121-285), sequential host code. field_stats, derived_fields and
+ * profile_direction are declared in cfd_abi.h. min / max start at data[0] and
+ * move on `<` / `>`; the sum runs in index order; avg = sum / count. The
+ * writers print the reference's text: a header row when create_new or the
+ * file is absent, else one appended row; the vel_mag columns only when
+ * derived->velocity_magnitude is set. The device-resident counterparts are
+ * hip_proj_derived_statistics / hip_proj_write_csv_* (projection_hip.h). */
+CFD_HIP_EXPORT field_stats calculate_field_statistics(const double* data, size_t count);
+CFD_HIP_EXPORT derived_fields* derived_fields_create(size_t nx, size_t ny, size_t nz);
+CFD_HIP_EXPORT void derived_fields_destroy(derived_fields* derived);
+CFD_HIP_EXPORT void derived_fields_clear(derived_fields* derived);
+CFD_HIP_EXPORT void derived_fields_compute_velocity_magnitude(derived_fields* derived,
+                                                              const flow_field* field);
+CFD_HIP_EXPORT void derived_fields_compute_statistics(derived_fields* derived,
+                                                      const flow_field* field);
+CFD_HIP_EXPORT void write_csv_timeseries(const char* filename, int step, double time,
+                                         const flow_field* field, const derived_fields* derived,
+                                         const ns_solver_params_t* params,
+                                         const ns_solver_stats_t* stats, size_t nx, size_t ny,
+                                         int create_new);
+CFD_HIP_EXPORT void write_csv_centerline(const char* filename, const flow_field* field,
+                                         const derived_fields* derived, const double* x_coords,
+                                         const double* y_coords, size_t nx, size_t ny,
+                                         profile_direction direction);
+CFD_HIP_EXPORT void write_csv_statistics(const char* filename, int step, double time,
+                                         const flow_field* field, const derived_fields* derived,
+                                         size_t nx, size_t ny, int create_new);
+
 /* ---- Poisson solver interface (poisson_solver.h:132-375, linear_solver.c:25-535)
  * Only POISSON_BACKEND_GPU solvers exist here (the CPU backends are the
  * reference's own); AUTO selects GPU when a HIP device is visible. The

@@ -351,6 +351,57 @@ CFD_HIP_EXPORT cfd_status_t cfd_hip_stream_bench_nm(int device, size_t n, int ni
 CFD_HIP_EXPORT cfd_status_t hip_proj_write_vtk(hip_proj_ctx_t* ctx, const char* filename,
                                                const grid* g, double rho0);
 
+/* ---- monitoring of the resident state (derived_fields.c:27-224,
+ * csv_output.c:121-285) without a field download: one streaming pass over the
+ * padded device fields (derived_stats.hip) reduces min / max / sum on the GPU.
+ * None of these entries changes device state or ends a resident (dirty_faces)
+ * run; single-device contexts only (Z-slab: CFD_ERROR_UNSUPPORTED). Additive:
+ * no ABI version change, no kernel timer.
+ *   min / max  ignore NaN (fmin / fmax); the reference's `<` / `>` loop does so
+ *              for every element but data[0]. A field of NaNs only reports
+ *              min = +inf, max = -inf. The sign of a zero min / max is
+ *              unspecified (the reference's own depends on the element order).
+ *   sum        a NaN or Inf in a field propagates into that field's sum. The
+ *              order is fixed (per thread, 64-lane tree, waves, workgroups in
+ *              index order): bit-identical from run to run, equal to the
+ *              reference's sequential sum up to rounding.
+ *   avg_val    sum_val / (double)count, count = nx*ny*nz.
+ * A field the context does not hold is a constant c (rho: rho0, T: 0.0, the
+ * conventions of hip_proj_write_vtk): min = max = c, sum = c * count. */
+/* Statistics of one resident field (hip_field_id_t); CFD_ERROR_INVALID for a
+ * field the context does not hold. */
+CFD_HIP_EXPORT cfd_status_t hip_proj_field_statistics(hip_proj_ctx_t* ctx, int field_id,
+                                                      field_stats* out);
+/* derived_fields_compute_statistics on the resident state in one fused pass:
+ * fills u/v/w/p/rho/T_stats, with with_vel_mag != 0 also vel_mag_stats of
+ * sqrt((u*u) + (v*v) + (w*w)) (derived_fields.c:175), and sets stats_computed.
+ * out->velocity_magnitude, nx, ny, nz are left alone. */
+CFD_HIP_EXPORT cfd_status_t hip_proj_derived_statistics(hip_proj_ctx_t* ctx, int with_vel_mag,
+                                                        double rho0, derived_fields* out);
+/* The velocity magnitude as nx*ny*nz packed doubles (reference layout). */
+CFD_HIP_EXPORT cfd_status_t hip_proj_velocity_magnitude(hip_proj_ctx_t* ctx, double* host);
+/* write_csv_timeseries / write_csv_statistics / write_csv_centerline of the
+ * resident state, the reference's text (host/csv_format.h). with_vel_mag
+ * selects the column set the reference writes when derived->velocity_magnitude
+ * is set. The timeseries row uses params->dt and stats->iterations / residual
+ * / elapsed_time_ms. The centerline gathers row j = ny/2 (PROFILE_HORIZONTAL)
+ * or column i = nx/2 (PROFILE_VERTICAL) of the k = 0 plane (the reference's
+ * IDX_2D index) on the device; g must match the context. */
+CFD_HIP_EXPORT cfd_status_t hip_proj_write_csv_timeseries(hip_proj_ctx_t* ctx,
+                                                          const char* filename, int step,
+                                                          double time,
+                                                          const ns_solver_params_t* params,
+                                                          const ns_solver_stats_t* stats,
+                                                          int with_vel_mag, int create_new);
+CFD_HIP_EXPORT cfd_status_t hip_proj_write_csv_statistics(hip_proj_ctx_t* ctx,
+                                                          const char* filename, int step,
+                                                          double time, double rho0,
+                                                          int with_vel_mag, int create_new);
+CFD_HIP_EXPORT cfd_status_t hip_proj_write_csv_centerline(hip_proj_ctx_t* ctx,
+                                                          const char* filename, const grid* g,
+                                                          profile_direction direction,
+                                                          double rho0, int with_vel_mag);
+
 /* Standalone pressure-Poisson solve on host buffers, the HIP counterpart of
  * poisson_solver_solve with a POISSON_BACKEND_GPU solver (linear_solver.c:487-509,
  * poisson_solver_cg_gpu.cu:135-178): upload x and rhs, solve lap(x) = rhs with
