@@ -781,6 +781,15 @@ class HipProjection:
             bv.ctypes.data_as(A.c_double_p) if bv is not None else None)
         return s, st
 
+    def dst_transform(self, field: np.ndarray, axis: int) -> int:
+        """hip_proj_dst_transform: the unnormalised type-I sine transform of
+        the interior of `field` along axis 0 (x), 1 (y) or 2 (z), in place
+        (one transform pass of HIP_POISSON_DST); returns the status."""
+        assert field.dtype == np.float64 and field.flags["C_CONTIGUOUS"]
+        assert field.shape == self.shape, (field.shape, self.shape)
+        return self._lib().hip_proj_dst_transform(self._ctx, field.ctypes.data_as(A.c_double_p),
+                                                  axis)
+
     def cg_fixed_iters(self, rhs: np.ndarray, dx, dy, dz, iters: int) -> float:
         a = np.ascontiguousarray(rhs, dtype=np.float64)
         return self._lib().hip_proj_cg_fixed_iters(self._ctx, a.ctypes.data_as(A.c_double_p),

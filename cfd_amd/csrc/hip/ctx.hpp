@@ -27,6 +27,14 @@ struct Rb2Dec;    // rb2.hpp
 struct BcgState;  // bicgstab.hpp
 }  // namespace cfdhip
 
+// Device tables of the sine-transform solver for one axis length n
+// (dst_solve.hpp): the zero-padded sine matrix (pitch np) and e_n
+struct DstTable {
+    int n, np;
+    double* S;
+    double* e;
+};
+
 // Error reporting goes through the host library's thread-local error state
 // (cfd_set_error, logging.c:39-46 in the reference). Weak, so the library
 // links against either the reference's host library or ours.
@@ -138,6 +146,10 @@ struct hip_proj_ctx : TilePlan {
     double *rhat = nullptr, *bs = nullptr, *bt = nullptr;
     BcgState* bcgst = nullptr;
     double* bcg_part = nullptr;
+    // sine-transform solver (dst_solve.hpp): the tables, cached per distinct
+    // axis length by the first such solve, and the events around a solve
+    std::vector<DstTable> dst_tabs;
+    hipEvent_t dst_ev[2] = {nullptr, nullptr};
     // monitoring (derived_stats.hip), allocated by the first such call: the
     // statistics pass's workgroup records, totals and ticket; the velocity
     // magnitude in the padded layout

@@ -1,0 +1,377 @@
+// dst_solve.hpp -- the direct sine-transform pressure solver (HIP_POISSON_DST).
+//
+// Inside a solve the boundary cells of x are frozen (the reference's CG
+// applies its BC to x only before and after the loop), so the interior system
+// is the constant-coefficient 7-point Laplacian with Dirichlet data. On the
+// uniform box the type-I sine transform along each axis diagonalises it:
+//   x = S_x S_y S_z [ norm / (lx[i] + ly[j] + lz[k]) * S_z S_y S_x b ],
+//   b = -rhs + (frozen boundary neighbours) / h^2,  norm = prod 2 / (n + 1).
+// Every transform is a dense product with the symmetric sine matrix S_n
+// (host/dst_tables.h) on the fp64 matrix cores (v_mfma_f64_16x16x4_f64):
+//   k_dst_strided  Y = S X along y or z: the 16 columns of a tile are 16
+//                  consecutive x cells, so the B operand is one 128-B load
+//                  per k row; A comes from the table (S is symmetric, so the
+//                  16 rows of a fragment are read as 16 consecutive entries
+//                  of table row k);
+//   k_dst_x        Y = X S along x: 32 rows of X are staged through LDS in
+//                  64-column chunks (coalesced loads), the A fragments are
+//                  read from there, B from the table; the first pass forms b
+//                  while it loads.
+// Both read and write interior cells only (never a pad column or a boundary
+// cell): out-of-range rows, columns and k steps are masked to zero on the
+// load and skipped on the store; the table is zero-padded to its 64-row tile.
+// The summation order is fixed, so a solve is bitwise reproducible.
+// Host code + kernels; private to projection_hip.hip (through
+// poisson_solve.hpp).
+#pragma once
+
+#include "ctx.hpp"
+#include "../host/dst_tables.h"
+
+namespace cfdhip {
+
+typedef double dst_d4 __attribute__((ext_vector_type(4)));
+
+// one strided pass: the transformed axis (n points, stride sa), 16-column
+// tiles along x (nc columns), nb batch lines of stride sb
+struct DstAxis {
+    int n, nc, nb;
+    long long sa, sb;
+    long long off0;  // the first interior cell of batch line 0
+    int np;          // table pitch
+    int tiles_a, tiles_c;
+};
+
+// the eigenvalue scaling of the last forward pass: norm / (la + lc + lb) with
+// l = e[index] * 1/h^2 along the pass's axis, its columns and its batch lines
+// (eb == nullptr: no third axis)
+struct DstScale {
+    const double* ea;
+    const double* ec;
+    const double* eb;
+    double ha, hc, hb, norm;
+};
+
+// the x pass: lines (j, k) of n = nx - 2 cells
+struct DstRows {
+    int n, nj, nk, k0;
+    long long px, ps;
+    int np;
+    int tiles_j, tiles_a;
+};
+
+constexpr int DST_TA = 64;   // k_dst_strided: output rows per wave (4 MFMA tiles)
+constexpr int DST_XR = 32;   // k_dst_x: lines per workgroup (2 MFMA tiles)
+constexpr int DST_XK = 64;   // k_dst_x: columns of X staged per chunk
+constexpr int DST_XP = 66;   // LDS row pitch: conflict-free fragment reads
+
+// Workgroup = 4 waves on one 64-row tile of the output and 4 adjacent
+// 16-column tiles (the waves share the table loads through the L1).
+template <bool SCALE>
+static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
+                                                            const double* __restrict__ S,
+                                                            const double* __restrict__ in,
+                                                            double* __restrict__ out,
+                                                            DstScale sc) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int t = blockIdx.x;
+    const int tc = t % g.tiles_c;
+    t /= g.tiles_c;
+    const int ta = t % g.tiles_a;
+    const int q = t / g.tiles_a;
+    if (q >= g.nb || tc * 64 + w * 16 >= g.nc) return;  // wave-uniform
+    const int a0 = ta * DST_TA;
+    const int col = tc * 64 + w * 16 + (lane & 15);
+    const int kq = lane >> 4;
+    const bool cin = col < g.nc;
+    const long long base = g.off0 + (long long)q * g.sb + col;
+    dst_d4 acc[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) acc[m] = dst_d4{0.0, 0.0, 0.0, 0.0};
+    const int kend = (g.n + 3) & ~3;
+    for (int b0 = 0; b0 < kend; b0 += 4) {
+        const int kk = b0 + kq;
+        double xv = 0.0;
+        if (cin && kk < g.n) xv = in[base + (long long)kk * g.sa];
+        const double* srow = S + (size_t)kk * g.np + a0 + (lane & 15);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+            acc[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(srow[16 * m], xv, acc[m], 0, 0, 0);
+    }
+    if (!cin) return;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int a = a0 + 16 * m + kq + 4 * r;
+            if (a >= g.n) continue;
+            double v = acc[m][r];
+            if (SCALE) {
+                double lam = (sc.ea[a] * sc.ha) + (sc.ec[col] * sc.hc);
+                if (sc.eb) lam += sc.eb[q] * sc.hb;
+                v *= sc.norm / lam;
+            }
+            out[base + (long long)a * g.sa] = v;
+        }
+    }
+}
+
+// Workgroup = 4 waves on 32 lines (consecutive j of one plane) x 256 output
+// columns, 64 per wave. FORM_B: the input is b = -rhs + (frozen boundary
+// neighbours of xb) / h^2, formed on the load (in = rhs).
+template <bool FORM_B>
+static __global__ __launch_bounds__(256) void k_dst_x(DstRows g, const double* __restrict__ S,
+                                                      const double* __restrict__ in,
+                                                      const double* __restrict__ xb,
+                                                      double* __restrict__ out, Lap L, int is3d) {
+    __shared__ double xs[DST_XR][DST_XP];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int t = blockIdx.x;
+    const int ta = t % g.tiles_a;
+    t /= g.tiles_a;
+    const int tj = t % g.tiles_j;
+    const int kq = t / g.tiles_j;  // 0 .. nk - 1
+    const int j0 = tj * DST_XR;    // interior line index
+    const long long plane = (long long)(g.k0 + kq) * g.ps;
+    const int a0w = ta * 256 + w * 64;
+    const bool wact = a0w < g.np;  // wave-uniform: this wave has output columns
+    dst_d4 acc[2][4];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = dst_d4{0.0, 0.0, 0.0, 0.0};
+    for (int b0 = 0; b0 < g.n; b0 += DST_XK) {
+        __syncthreads();  // the previous chunk's fragments are read
+#pragma unroll
+        for (int u = 0; u < DST_XR * DST_XK / 256; ++u) {
+            const int e = (int)threadIdx.x + 256 * u;
+            const int row = e >> 6, bl = e & 63;
+            const int b = b0 + bl, jj = j0 + row;
+            double v = 0.0;
+            if (jj < g.nj && b < g.n) {
+                const long long idx = plane + (long long)(jj + 1) * g.px + (b + 1);
+                if (FORM_B) {
+                    v = -in[idx];
+                    if (b == 0) v += xb[idx - 1] * L.dx2_inv;
+                    if (b == g.n - 1) v += xb[idx + 1] * L.dx2_inv;
+                    if (jj == 0) v += xb[idx - g.px] * L.dy2_inv;
+                    if (jj == g.nj - 1) v += xb[idx + g.px] * L.dy2_inv;
+                    if (is3d) {
+                        if (kq == 0) v += xb[idx - g.ps] * L.inv_dz2;
+                        if (kq == g.nk - 1) v += xb[idx + g.ps] * L.inv_dz2;
+                    }
+                } else {
+                    v = in[idx];
+                }
+            }
+            xs[row][bl] = v;
+        }
+        __syncthreads();
+        if (!wact) continue;
+        const int kc = min(DST_XK, (g.n - b0 + 3) & ~3);
+        for (int s = 0; s < kc; s += 4) {
+            const int kk = s + (lane >> 4);
+            const double a_lo = xs[lane & 15][kk];
+            const double a_hi = xs[16 + (lane & 15)][kk];
+            const double* srow = S + (size_t)(b0 + kk) * g.np + a0w + (lane & 15);
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                const double bv = srow[16 * ni];
+                acc[0][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_lo, bv, acc[0][ni], 0, 0, 0);
+                acc[1][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a_hi, bv, acc[1][ni], 0, 0, 0);
+            }
+        }
+    }
+    if (!wact) return;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int jj = j0 + mi * 16 + (lane >> 4) + 4 * r;
+            if (jj >= g.nj) continue;
+            const long long rowi = plane + (long long)(jj + 1) * g.px + 1;
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) {
+                const int a = a0w + 16 * ni + (lane & 15);
+                if (a < g.n) out[rowi + a] = acc[mi][ni][r];
+            }
+        }
+    }
+}
+
+}  // namespace cfdhip
+
+// The cached tables of one axis length (device copies)
+static cfd_status_t dst_table(hip_proj_ctx* c, int n, const DstTable** out) {
+    for (const DstTable& t : c->dst_tabs)
+        if (t.n == n) {
+            *out = &t;
+            return CFD_SUCCESS;
+        }
+    const size_t np = dst_table_pitch((size_t)n);
+    std::vector<double> hs(np * np), he((size_t)n);
+    dst_fill_sine_table((size_t)n, hs.data());
+    dst_fill_eigenvalues((size_t)n, he.data());
+    DstTable t{n, (int)np, nullptr, nullptr};
+    HIP_TRY(hipMalloc((void**)&t.S, hs.size() * sizeof(double)));
+    c->dst_tabs.push_back(t);  // owned by the context from here (free_ctx)
+    HIP_TRY(hipMalloc((void**)&c->dst_tabs.back().e, he.size() * sizeof(double)));
+    // pageable sources: synchronous copies (ordered before later stream work)
+    HIP_TRY(hipMemcpy(c->dst_tabs.back().S, hs.data(), hs.size() * sizeof(double),
+                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->dst_tabs.back().e, he.data(), he.size() * sizeof(double),
+                      hipMemcpyHostToDevice));
+    *out = &c->dst_tabs.back();
+    return CFD_SUCCESS;
+}
+
+// the tables of the context's axes (tz == nullptr in 2-D); the vector may
+// grow while they are looked up, so the pointers are taken afterwards
+struct DstTabs {
+    const DstTable *tx, *ty, *tz;
+};
+
+static cfd_status_t dst_tables_of(hip_proj_ctx* c, DstTabs* T) {
+    const DstTable* t = nullptr;
+    const int n[3] = {(int)c->nx - 2, (int)c->ny - 2, c->nz > 1 ? (int)c->nz - 2 : 0};
+    for (int a = 0; a < 3; ++a)
+        if (n[a] > 0) ST_TRY(dst_table(c, n[a], &t));
+    ST_TRY(dst_table(c, n[0], &T->tx));
+    ST_TRY(dst_table(c, n[1], &T->ty));
+    T->tz = nullptr;
+    if (n[2] > 0) ST_TRY(dst_table(c, n[2], &T->tz));
+    return CFD_SUCCESS;
+}
+
+// One unnormalised DST-I pass of the interior along `axis` (0 x, 1 y, 2 z):
+// in -> out (distinct fields). form_b (axis 0): the input is b formed from
+// in = rhs and the shell of xb. sc (axes 1, 2): the eigenvalue scaling on the
+// store.
+static void dst_pass(hip_proj_ctx* c, const DstTabs& T, int axis, const double* in, double* out,
+                     const DstScale* sc = nullptr, const double* xb = nullptr,
+                     const Lap* L = nullptr) {
+    const bool is3d = c->nz > 1;
+    const int k0 = is3d ? 1 : 0;
+    const int nk = is3d ? (int)c->nz - 2 : 1;
+    if (axis == 0) {
+        DstRows g;
+        g.n = (int)c->nx - 2;
+        g.nj = (int)c->ny - 2;
+        g.nk = nk;
+        g.k0 = k0;
+        g.px = c->px;
+        g.ps = c->ps;
+        g.np = T.tx->np;
+        g.tiles_j = (g.nj + DST_XR - 1) / DST_XR;
+        g.tiles_a = (g.n + 255) / 256;
+        const dim3 grid((unsigned)(g.tiles_a * g.tiles_j * g.nk));
+        if (xb)
+            klaunch(c, k_dst_x<true>, grid, dim3(256), g, T.tx->S, in, xb, out, *L, is3d ? 1 : 0);
+        else
+            klaunch(c, k_dst_x<false>, grid, dim3(256), g, T.tx->S, in, nullptr, out, Lap{}, 0);
+        return;
+    }
+    const DstTable* t = (axis == 1) ? T.ty : T.tz;
+    DstAxis g;
+    g.n = t->n;
+    g.nc = (int)c->nx - 2;
+    g.np = t->np;
+    if (axis == 1) {
+        g.nb = nk;
+        g.sa = c->px;
+        g.sb = c->ps;
+        g.off0 = (long long)k0 * c->ps + c->px + 1;
+    } else {
+        g.nb = (int)c->ny - 2;
+        g.sa = c->ps;
+        g.sb = c->px;
+        g.off0 = c->ps + c->px + 1;
+    }
+    g.tiles_a = g.np / DST_TA;
+    g.tiles_c = (g.nc + 63) / 64;
+    const dim3 grid((unsigned)(g.tiles_c * g.tiles_a * g.nb));
+    if (sc) klaunch(c, k_dst_strided<true>, grid, dim3(256), g, t->S, in, out, *sc);
+    else klaunch(c, k_dst_strided<false>, grid, dim3(256), g, t->S, in, out, DstScale{});
+}
+
+// ---------------------------------------------------------------------------
+// The solve: x in c->pn, rhs in c->rhs. The transforms ping-pong between
+// c->xt and the interior of c->pn (whose values are not needed once b is
+// formed; its shell is never written), so rhs stays intact for the final
+// residual. r0 and both residual norms come from k_cg_setup (r = -rhs +
+// lap(x) on the interior, with x's boundary as it stands). max_iterations,
+// check_interval and omega play no part.
+// ---------------------------------------------------------------------------
+static cfd_status_t dst_solve(hip_proj_ctx* c, double dx, double dy, double dz, double rel_tol,
+                              double abs_tol) {
+    const bool is3d = c->nz > 1;
+    const Lap L = make_lap(dx, dy, is3d ? dz : 0.0);
+    const int G = tile_grid(c);
+    const DirVals dv{};
+    double* x = c->pn;
+    ST_TRY(ensure_aux(c, true, true));
+    DstTabs T;
+    ST_TRY(dst_tables_of(c, &T));
+    for (hipEvent_t& e : c->dst_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(c->dst_ev[0], c->stream));
+    // poisson_solver_apply_bc(x) at solve start, as cg_solve: the default
+    // Neumann shell, or the caller's boundary left as it is
+    const bool neumann = (c->poisson_bc == HIP_POISSON_BC_NEUMANN);
+    if (neumann) launch_bc(c, x, 0, dv);
+    auto residual = [&](CgState* s) -> cfd_status_t {
+        timed(c, HIP_KT_CG_SETUP, [&] {
+            klaunch(c, k_cg_setup<false, false, true, false>, dim3(G), dim3(NT), c->geo, L,
+                    DivCoef{}, nullptr, nullptr, nullptr, c->rhs, x, c->r, c->st, c->partials,
+                    c->counter, rel_tol, abs_tol, 1, 1, c->dsum, nullptr);
+        });
+        return poll_final(c, c->st, s);
+    };
+    CgState s0;
+    ST_TRY(residual(&s0));
+    c->pstats.initial_residual = s0.res0;
+    if (s0.res0 < abs_tol) {  // linear_solver_cg.c:353-361: no end BC
+        flush_timing(c);
+        c->pstats.status = POISSON_CONVERGED;
+        c->pstats.iterations = 0;
+        c->pstats.final_residual = s0.res0;
+        c->pstats.elapsed_time_ms = 0.0;
+        return CFD_SUCCESS;
+    }
+    DstScale sc{};
+    sc.norm = (2.0 / (double)(c->nx - 1)) * (2.0 / (double)(c->ny - 1));
+    if (is3d) sc.norm *= 2.0 / (double)(c->nz - 1);
+    sc.ec = T.tx->e;
+    sc.hc = L.dx2_inv;
+    dst_pass(c, T, 0, c->rhs, c->xt, nullptr, x, &L);
+    if (is3d) {
+        sc.ea = T.tz->e, sc.ha = L.inv_dz2;
+        sc.eb = T.ty->e, sc.hb = L.dy2_inv;
+        dst_pass(c, T, 1, c->xt, x);
+        dst_pass(c, T, 2, x, c->xt, &sc);
+        dst_pass(c, T, 2, c->xt, x);
+        dst_pass(c, T, 1, x, c->xt);
+    } else {
+        sc.ea = T.ty->e, sc.ha = L.dy2_inv;
+        sc.eb = nullptr, sc.hb = 0.0;
+        dst_pass(c, T, 1, c->xt, x, &sc);
+        dst_pass(c, T, 1, x, c->xt);
+    }
+    dst_pass(c, T, 0, c->xt, x);
+    // || b - A x || with the boundary still frozen
+    CgState s1;
+    ST_TRY(residual(&s1));
+    if (neumann) launch_bc(c, x, 0, dv);  // linear_solver_cg.c:447
+    HIP_TRY(hipEventRecord(c->dst_ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->dst_ev[1]));
+    flush_timing(c);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->dst_ev[0], c->dst_ev[1]));
+    const double res = s1.res0;
+    const bool conv = (res < s0.tol) || (res < abs_tol);
+    c->pstats.status = conv ? POISSON_CONVERGED : POISSON_MAX_ITER;
+    c->pstats.iterations = 1;
+    c->pstats.final_residual = res;
+    c->pstats.elapsed_time_ms = (double)ms;
+    return conv ? CFD_SUCCESS : CFD_ERROR_MAX_ITER;
+}

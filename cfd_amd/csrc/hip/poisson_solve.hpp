@@ -1,6 +1,7 @@
 // poisson_solve.hpp -- the pressure solvers of the device context (CG in its
-// textbook and single-reduction forms, BiCGSTAB, the relaxation methods) with
-// their launch wrappers and the polled device loop they share. Host code
+// textbook and single-reduction forms, BiCGSTAB, the relaxation methods, and
+// through dst_solve.hpp the direct sine-transform solve) with their launch
+// wrappers and the polled device loop they share. Host code
 // only; private to projection_hip.hip, which includes it after the kernels.
 #pragma once
 
@@ -1059,3 +1060,6 @@ static cfd_status_t ensure_aux(hip_proj_ctx* c, bool need_rhs, bool need_xt) {
     }
     return CFD_SUCCESS;
 }
+
+// the direct sine-transform solver: uses ensure_aux and the poll helpers above
+#include "dst_solve.hpp"

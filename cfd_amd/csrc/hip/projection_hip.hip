@@ -118,6 +118,12 @@ static void free_ctx(hip_proj_ctx* c) {
     if (c->rb2dec) hipFree(c->rb2dec);
     if (c->bcgst) hipFree(c->bcgst);
     if (c->bcg_part) hipFree(c->bcg_part);
+    for (const DstTable& t : c->dst_tabs) {
+        if (t.S) hipFree(t.S);
+        if (t.e) hipFree(t.e);
+    }
+    for (hipEvent_t e : c->dst_ev)
+        if (e) hipEventDestroy(e);
     if (c->partials) hipFree(c->partials);
     if (c->counter) hipFree(c->counter);
     if (c->red) hipFree(c->red);
@@ -761,6 +767,15 @@ void ctx_queue_max_T(hip_proj_ctx* c) {
                        c->stream, c->geo, c->T, c->red + 3, ks);
 }
 
+// The sine-transform solve works on whole z lines: a Z-slab context is
+// refused before anything is uploaded or launched (as BiCGSTAB's refusals).
+static cfd_status_t dst_refuse_slab(const hip_proj_ctx* c, int method) {
+    if (method != HIP_POISSON_DST || !dist(c)) return CFD_SUCCESS;
+    set_err(CFD_ERROR_UNSUPPORTED,
+            "projection_hip: the DST pressure solve runs on one device, not on Z-slabs");
+    return CFD_ERROR_UNSUPPORTED;
+}
+
 extern "C" {
 
 static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
@@ -769,6 +784,7 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
     if (!c) return CFD_ERROR_INVALID;
     cfd_status_t s = ctx_validate_params(c, g, prm);
     if (s != CFD_SUCCESS) return s;
+    ST_TRY(dst_refuse_slab(c, c->cfg.poisson_method));
     HIP_TRY(hipSetDevice(c->device));
     const size_t nz = c->nzg;
     const double dx = g->dx[0], dy = g->dy[0];
@@ -857,9 +873,13 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
         if (method == HIP_POISSON_JACOBI)
             HIP_TRY(hipMemsetAsync(c->xt, 0, field_elems(c) * sizeof(double), c->stream));
         int maxit = c->cfg.poisson_max_iter;
-        ps = relax_solve(c, method, dx, dy, dz, c->cfg.poisson_tolerance,
-                         c->cfg.poisson_abs_tolerance, maxit,
-                         std::max(1, c->cfg.poisson_check_interval), c->cfg.sor_omega);
+        if (method == HIP_POISSON_DST)
+            ps = dst_solve(c, dx, dy, dz, c->cfg.poisson_tolerance,
+                           c->cfg.poisson_abs_tolerance);
+        else
+            ps = relax_solve(c, method, dx, dy, dz, c->cfg.poisson_tolerance,
+                             c->cfg.poisson_abs_tolerance, maxit,
+                             std::max(1, c->cfg.poisson_check_interval), c->cfg.sor_omega);
     }
     if (ps == CFD_ERROR_MAX_ITER && !c->cfg.poisson_fail_fatal) ps = CFD_SUCCESS;
     if (ps != CFD_SUCCESS) {
@@ -958,6 +978,7 @@ static cfd_status_t host_steps(hip_proj_ctx_t* c, flow_field* f, const grid* g,
     if (f->nx < 3 || f->ny < 3 || (f->nz > 1 && f->nz < 3)) return CFD_ERROR_INVALID;
     cfd_status_t s = ctx_validate_params(c, g, prm);
     if (s != CFD_SUCCESS) return s;
+    ST_TRY(dst_refuse_slab(c, c->cfg.poisson_method));
     if (n_steps <= 0) return CFD_SUCCESS;
     const bool need_T = (prm->beta != 0.0) || (prm->alpha > 0.0);
     const bool shell = shell_ok && c->cfg.dirty_faces > 0 && ctx_shell_fits(c, 2);
@@ -1157,6 +1178,7 @@ cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* c, int method, double* x,
             return CFD_ERROR_UNSUPPORTED;
         }
     }
+    ST_TRY(dst_refuse_slab(c, method));
     HIP_TRY(hipSetDevice(c->device));
     if (bc_mode == HIP_POISSON_BC_FIXED) {
         if (!c->bcfix) ST_TRY(dalloc(c, &c->bcfix, field_elems(c)));
@@ -1203,6 +1225,8 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
         s = cg_solve(c, dx, dy, dz, dc, RHS_FROM_ARRAY, rel, abs_tol, maxit, ci, true);
     } else if (method == HIP_POISSON_BICGSTAB) {
         s = bicgstab_solve(c, dx, dy, dz, rel, abs_tol, maxit, ci);
+    } else if (method == HIP_POISSON_DST) {
+        s = dst_solve(c, dx, dy, dz, rel, abs_tol);
     } else {
         s = relax_solve(c, method, dx, dy, dz, rel, abs_tol, maxit, ci, omega);
     }
@@ -1212,9 +1236,42 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (stats) {
         *stats = c->pstats;
-        stats->elapsed_time_ms = 0.0;
+        // the direct solve reports its device time (events around the solve)
+        if (method != HIP_POISSON_DST) stats->elapsed_time_ms = 0.0;
     }
     return s;
+}
+
+cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* c, double* field_host, int axis) {
+    GroupHostLock hl_(c);
+    if (!c || !field_host) return CFD_ERROR_INVALID;
+    if (axis < 0 || axis > 2) {
+        set_err(CFD_ERROR_INVALID, "hip_proj_dst_transform: axis must be 0 (x), 1 (y) or 2 (z)");
+        return CFD_ERROR_INVALID;
+    }
+    if (axis == 2 && c->nz == 1) {
+        set_err(CFD_ERROR_INVALID, "hip_proj_dst_transform: a 2-D context has no z axis");
+        return CFD_ERROR_INVALID;
+    }
+    ST_TRY(dst_refuse_slab(c, HIP_POISSON_DST));
+    c->resident = 0;  // the transform runs in the step's pressure buffers
+    HIP_TRY(hipSetDevice(c->device));
+    ST_TRY(ensure_aux(c, false, true));
+    DstTabs T;
+    ST_TRY(dst_tables_of(c, &T));
+    // the input goes to both fields: the pass reads the interior of one and
+    // writes the interior of the other, whose boundary is the caller's
+    for (double* d : {c->pn, c->xt})
+        HIP_TRY(hipMemcpy2DAsync(d, c->px * sizeof(double), field_host, c->nx * sizeof(double),
+                                 c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
+                                 c->stream));
+    dst_pass(c, T, axis, c->pn, c->xt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(field_host, c->nx * sizeof(double), c->xt, c->px * sizeof(double),
+                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CFD_SUCCESS;
 }
 
 double hip_proj_cg_fixed_iters(hip_proj_ctx_t* c, const double* rhs_host, double dx, double dy,

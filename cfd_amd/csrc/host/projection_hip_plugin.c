@@ -85,6 +85,13 @@ static cfd_status_t get_ctx(ns_solver_t* solver, const grid* g, hip_proj_ctx_t**
             cfg.dirty_faces = 1;
             cfg.dirty_sync_interval = atoi(e);
         }
+        /* CFD_HIP_POISSON=dst: the `projection_hip` name solves the pressure
+         * equation with the direct sine-transform method (HIP_POISSON_DST); the
+         * reference's method enum has no direct method to ask for it with */
+        const char* pm = getenv("CFD_HIP_POISSON");
+        if (pm && strcmp(pm, "dst") == 0 && solver->name &&
+            strcmp(solver->name, NS_SOLVER_TYPE_PROJECTION_HIP) == 0)
+            cfg.poisson_method = HIP_POISSON_DST;
         pc->ctx = hip_proj_create(g->nx, g->ny, g->nz, &cfg);
         if (!pc->ctx) return CFD_ERROR_UNSUPPORTED;
     }

@@ -51,7 +51,16 @@ typedef enum {
     /* BiCGSTAB, linear_solver_bicgstab.c:265-495. A method of
      * hip_proj_poisson_solve / _ex only (BC_NEUMANN or BC_NONE, one device,
      * cg_variant 0); hip_proj_config_t.poisson_method does not take it. */
-    HIP_POISSON_BICGSTAB = 3
+    HIP_POISSON_BICGSTAB = 3,
+    /* Direct solve by type-I sine transforms along each axis (the interior
+     * system of a solve is the constant-coefficient Laplacian with the
+     * boundary of x frozen, which the transforms diagonalise exactly). One
+     * device, all three bc_modes of hip_proj_poisson_solve_ex, and a
+     * hip_proj_config_t.poisson_method of the projection step. max_iterations,
+     * check_interval and omega are ignored; stats: iterations 1 (0 when the
+     * initial residual is below absolute_tolerance), the 2-norm residuals of
+     * CG, status by CG's rule on the final residual, elapsed_time_ms. */
+    HIP_POISSON_DST = 4
 } hip_poisson_method_t;
 
 /* Device/solver configuration (role of gpu_config_t, gpu_device.h:32-53). The
@@ -438,6 +447,18 @@ CFD_HIP_EXPORT cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* ctx, int m
                                                       const poisson_solver_params_t* params,
                                                       poisson_solver_stats_t* stats, int bc_mode,
                                                       const double* bc_values);
+
+/* One transform pass of HIP_POISSON_DST on its own: the unnormalised type-I
+ * sine transform of the interior of field_host (nx*ny*nz host doubles) along
+ * axis 0 (x), 1 (y) or 2 (z), in place,
+ *   y[a] = sum_b sin(pi (a + 1)(b + 1) / (n + 1)) x[b],  a, b = 0 .. n - 1
+ * over the n interior cells of every line of that axis; boundary cells are
+ * left as they are. Applied twice it returns (n + 1) / 2 times the input.
+ * CFD_ERROR_INVALID for another axis and for axis 2 on a 2-D context,
+ * CFD_ERROR_UNSUPPORTED on a Z-slab context. Uses the solve's work fields
+ * (ends a resident run, like hip_proj_poisson_solve). */
+CFD_HIP_EXPORT cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* ctx, double* field_host,
+                                                   int axis);
 
 /* ---- Z-slab multi-GPU ------------------------------------------------------
  * The reference runs one device per simulation (solver_projection_gpu.cu has
