@@ -6,7 +6,11 @@ the Makefile embeds it in the library as hip_proj_build_id() and
 cfd_amd._native refuses a library whose id differs from the sources beside it.
 `kernel_source_sha()` hashes the HIP sources only, and `device_code_sha(lib)`
 the device code inside a built library: PMC profiles are keyed on both
-(their byte counts depend on the kernels, not on host code). The HIP sources
+(their byte counts depend on the kernels, not on host code). A header that
+defines kernels (kernels.hpp, relax_kernels.hpp, rk_kernels.hpp, ccf.hpp,
+rb2.hpp, bicgstab.hpp, dst_solve.hpp) is compiled by one translation unit, so
+the library holds one code object per unit and every device function once
+(tests/test_device_symbols.py). The HIP sources
 also hold host code, so a host-only edit changes the first key. It leaves the
 second unchanged only while it keeps the order in which the host code first
 refers to each kernel instantiation: the compiler lays the kernels out in

@@ -1,10 +1,61 @@
 // bc_gpu.hip -- the reference's device-pointer BC entry points
 // (boundary_conditions_gpu.cuh:32-151, impl boundary/gpu/boundary_conditions_gpu.cu)
 // on caller-owned packed arrays: one k_bc_shell launch (pure gathers from
-// interior cells, kernels.hpp) per field on the caller's stream.
+// interior cells) per field on the caller's stream; and the library's own
+// launches of k_bc_shell on a context's field (launch_bc), so that the kernel
+// is emitted by this unit only. The shell enumeration it shares with
+// k_rx_shell and the step's shell passes is in device_util.hpp.
 #include "ctx.hpp"
 
 #include "cfd_hip/boundary_conditions_gpu.h"
+
+namespace cfdhip {
+
+// ---------------------------------------------------------------------------
+// Boundary conditions as pure gathers from interior cells (race-free):
+//   Neumann  (boundary_conditions_core_impl.h:41-85): c -> clamp(c, 1, n-2)
+//   Periodic (:90-134):                               0 -> n-2, n-1 -> 1
+// The reference applies x faces, then y faces, then z faces in place; the
+// composition of those copies is exactly this per-coordinate map, edges and
+// corners included. Dirichlet (:139-186) keeps the z > y > x face precedence.
+// Threads cover the boundary shell: z faces (3-D) plus the x/y ring of every
+// plane. mode: 0 Neumann, 1 periodic, 2 Dirichlet.
+// ---------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void k_bc_shell(Geo g, double* __restrict__ f, int mode,
+                                                  DirVals dv) {
+    const long long total = shell_total(g);
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+         e += (long long)gridDim.x * blockDim.x) {
+        int i, j, k;
+        bool zlo, zhi;
+        shell_cell(g, e, i, j, k, zlo, zhi);
+        const long long dst = cidx(g, i, j, k);
+        if (mode == 2) {
+            double v;
+            if (zlo) v = dv.back;
+            else if (zhi) v = dv.front;
+            else if (j == 0) v = dv.bottom;
+            else if (j == g.ny - 1) v = dv.top;
+            else if (i == 0) v = dv.left;
+            else v = dv.right;
+            f[dst] = v;
+        } else {
+            int si = bc_map(i, g.nx, mode), sj = bc_map(j, g.ny, mode);
+            int sk = (zlo || zhi) ? bc_map(k, g.nz, mode) : k;
+            f[dst] = f[cidx(g, si, sj, sk)];
+        }
+    }
+}
+
+}  // namespace cfdhip
+
+void launch_bc_geo(hip_proj_ctx* c, const Geo& g, double* f, int mode, const DirVals& dv) {
+    klaunch(c, k_bc_shell, dim3(shell_blocks(c)), dim3(256), g, f, mode, dv);
+}
+
+void launch_bc(hip_proj_ctx* c, double* f, int mode, const DirVals& dv) {
+    launch_bc_geo(c, c->geo, f, mode, dv);
+}
 
 namespace {
 

@@ -1,10 +1,13 @@
 // ctx.hpp -- the device context behind the hip_proj_* C-ABI and the helpers
 // shared by its translation units (projection_hip.hip: projection step, with
-// the Poisson solvers of poisson_solve.hpp; rk4_hip.hip: the RK4 integrator).
-// Private to the library.
+// the Poisson solvers of poisson_solve.hpp; rk4_hip.hip: the RK4 integrator;
+// and the I/O, checkpoint, statistics and BC units). It brings in no kernel:
+// a header that defines kernels (kernels.hpp, rk_kernels.hpp) is included by
+// the one unit that launches them, so every device function of the library
+// is emitted once. Private to the library.
 #pragma once
 
-#include "kernels.hpp"
+#include "device_util.hpp"
 #include "slab_comm.hpp"
 
 #include "cfd_hip/projection_hip.h"
@@ -56,8 +59,6 @@ static inline void set_err(cfd_status_t s, const char* msg) {
         }                                                                          \
     } while (0)
 
-namespace {
-
 struct TimedLaunch {
     hipEvent_t a, b;
     int kind;
@@ -70,8 +71,6 @@ struct TimedLaunch {
 struct alignas(16) PollSlot {
     unsigned char bytes[128];
 };
-
-}  // namespace
 
 // The launch geometry (px, ps, geo, the SGeos, the split and variant flags,
 // stagger_bytes, n_partials) is the TilePlan base, planned once in init_ctx.
@@ -343,20 +342,16 @@ static void with_int(int v, F&& f) {
     if (!(... || (v == Vs && (f(IntC<Vs>{}), true)))) f(IntC<V0>{});
 }
 
-static void launch_bc(hip_proj_ctx* c, double* f, int mode, const DirVals& dv) {
-    klaunch(c, k_bc_shell, dim3(shell_blocks(c)), dim3(256), c->geo, f, mode, dv);
-}
-
-static __global__ void k_init_red(unsigned long long* red) {
-    if (threadIdx.x == 0) {
-        red[0] = 0x8000000000000000ull;  // enc(+0.0): reference maxima start at 0.0
-        red[1] = 0x8000000000000000ull;
-        red[2] = 0ull;
-        red[5] = 0ull;
-        red[3] = 0x000FFFFFFFFFFFFFull;  // enc(-inf)
-        red[4] = 0x8000000000000000ull;
-    }
-}
+// Launches that several units share, each defined next to its kernel.
+// k_bc_shell on field f (bc_gpu.hip): with the context's geometry, or, for
+// the periodic-z slab form of hip_proj_apply_scalar_bc, with a geometry g of
+// the caller's
+void launch_bc(hip_proj_ctx* c, double* f, int mode, const DirVals& dv)
+    __attribute__((visibility("hidden")));
+void launch_bc_geo(hip_proj_ctx* c, const Geo& g, double* f, int mode, const DirVals& dv)
+    __attribute__((visibility("hidden")));
+// k_init_red on c->red: the maxima and flags of a step (projection_hip.hip)
+void launch_init_red(hip_proj_ctx* c) __attribute__((visibility("hidden")));
 
 static double ord_dec(unsigned long long e) {
     unsigned long long b = (e & 0x8000000000000000ull) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
@@ -449,6 +444,15 @@ struct GroupHostLock {
 };
 
 
+// The relaxation pressure solves on ctx->pn (relax_solve.hip), and the load of
+// that unit's code object at the creation of a Z-slab relaxation context.
+cfd_status_t relax_solve(hip_proj_ctx* c, int method, double dx, double dy, double dz,
+                         double rel_tol, double abs_tol, int max_iter, int check_interval,
+                         double omega_in) __attribute__((visibility("hidden")));
+bool relax_preload() __attribute__((visibility("hidden")));
+// The lazily allocated rhs / x_tmp fields (projection_hip.hip, before init_ctx).
+cfd_status_t ensure_aux(hip_proj_ctx* c, bool need_rhs, bool need_xt)
+    __attribute__((visibility("hidden")));
 // Shared by the integrators (defined in projection_hip.hip).
 cfd_status_t ctx_apply_thermal_bcs(hip_proj_ctx* c, const ns_thermal_bc_config_t& t, bool is3d)
     __attribute__((visibility("hidden")));

@@ -16,7 +16,7 @@
 // file is compiled with -ffp-contract=off), which an optional output array
 // receives with non-temporal 16-B stores in the padded layout.
 //
-// Reduction (kernels.hpp's scheme, 21 scalars): the per-thread order above, a
+// Reduction (device_util.hpp's scheme, 21 scalars): the per-thread order above, a
 // fixed 64-lane shuffle tree, the four waves in order, one record of 21
 // values per workgroup stored by one lane with agent-scope relaxed
 // (write-through) stores, s_waitcnt vmcnt(0), a ticket; the last workgroup

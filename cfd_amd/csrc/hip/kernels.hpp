@@ -1,202 +1,16 @@
-// kernels.hpp -- gfx950 device code for the Chorin projection step.
-//
-// Layout in HBM: every field is an SoA fp64 array with a padded row pitch
-// `px` (multiple of 8 doubles = 64 B) and plane pitch `ps` = px*ny, x fastest.
-// The reference layout idx = k*nx*ny + j*nx + i (lib/include/cfd/core/indexing.h)
-// is recovered with px = nx; uploads/downloads convert with 2-D copies.
-//
-// Stencil sweeps use 2.5-D tiles: a 256-thread workgroup owns a 64 (x) by 4 (y)
-// column tile and marches a chunk of `kc` planes in z, keeping the k-1/k/k+1
-// values of its own column in registers so each plane is read once from HBM;
-// x/y neighbours come from the L1/L2 lines the neighbouring lanes and waves
-// of the same tile just loaded. One wavefront = one 64-wide x row, so every
-// load is a fully coalesced 512-B row segment.
-//
-// Reductions are deterministic: per-thread sums in a fixed k order, a fixed
-// 64-lane shuffle tree, a fixed cross-wave order, one partial per workgroup,
-// and the last-arriving workgroup (agent-scope ticket) sums the partials in
-// index order. The partial hand-off follows the sc1 write-through protocol
-// (MI355X_MICROARCH.md "Valid forms", first table row): one lane stores the
-// partial with an agent-scope relaxed store, waits vmcnt(0), then takes the
-// ticket; the last workgroup reads every partial with agent-scope loads.
-//
-// All arithmetic is written in the reference's operation order and the file
-// is compiled with -ffp-contract=off, so every per-cell value is bitwise the
-// reference's; only the summation order of the CG dot products differs.
+// kernels.hpp -- the gfx950 kernels of the projection step and of its CG
+// pressure solve: the CG sweeps and the small-grid CG, the energy and thermal
+// kernels, the predictor and corrector. Included by one translation unit
+// only, projection_hip.hip (through poisson_solve.hpp), so that its
+// non-template kernels are emitted once. What other units share with it is in
+// device_util.hpp; the relaxation kernels are in relax_kernels.hpp
+// (relax_solve.hip), the integrators' in rk_kernels.hpp (rk4_hip.hip) and
+// k_bc_shell in bc_gpu.hip.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "mbox.hpp"
-#include "tile_plan.hpp"
+#include "device_util.hpp"
 
 namespace cfdhip {
-
-// TX x TY: the tile of the grid-stride kernels (tile_plan.hpp)
-constexpr int NT = TX * TY;  // threads per workgroup
-constexpr int NWAVE = NT / 64;
-
-// Poisson status codes (poisson_solver.h:83-89)
-constexpr int ST_CONVERGED = 0;
-constexpr int ST_MAX_ITER = 1;
-constexpr int ST_STAGNATED = 3;
-
-struct Lap {
-    double dx2_inv, dy2_inv, inv_dz2;  // linear_solver_cg.c:103-110
-};
-
-// x is updated every CG_XFOLD iterations: sweep A of iteration it with
-// it % CG_XFOLD == 0, it > 0, folds the CG_XFOLD pending alpha_j p_j
-// (j = it - 4 .. it - 1) into x before p_it overwrites slot it % CG_XFOLD;
-// the search directions live in a ring of CG_XFOLD buffers (p_j in [j % CG_XFOLD]).
-// A solve that stops after iteration it therefore leaves it % CG_XFOLD + 1
-// (1 .. CG_XFOLD) updates pending, in distinct ring slots, for k_cg_finalize.
-constexpr int CG_XFOLD = 4;
-
-// Device-resident CG state; written only by the finishing (last) workgroup.
-struct CgState {
-    double rho;     // (r, r) of the current residual
-    double alpha[CG_XFOLD];  // alpha_j of iteration j at [j % CG_XFOLD]
-    double beta;    // beta for the next sweep A
-    double pAp;
-    double res;     // current residual 2-norm
-    double res0;    // initial residual
-    double tol;     // max(rel_tol * res0, abs_tol)
-    double abs_tol;
-    int iterations; // completed iterations (reference stats->iterations)
-    int done;       // no further iteration may run
-    int status;     // poisson_solver_status_t
-    int nalpha;     // iterations whose alpha is valid (x must hold alpha_j p_j, j < nalpha)
-    int xdone;      // x holds alpha_j p_j for j < xdone (folded by sweep B)
-    int max_iter;
-    int check_interval;
-    int pad0;
-};
-
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-typedef __attribute__((address_space(1))) unsigned int gu32;
-
-__device__ __forceinline__ void store_sc1(double* p, double v) {
-    __hip_atomic_store((gu64*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double load_sc1(const double* p) {
-    unsigned long long b =
-        __hip_atomic_load((gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return __longlong_as_double((long long)b);
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-
-// Sum over the workgroup; result valid in thread 0. `sh` holds NWAVE doubles.
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < NWAVE; ++w) s += sh[w];
-    }
-    __syncthreads();
-    return s;
-}
-
-// Grid-wide deterministic sum. Returns true (in every thread) for the
-// last-arriving workgroup; its thread 0 then holds the grid total.
-__device__ __forceinline__ bool grid_sum_last(double block_total, double* partials,
-                                              unsigned* counter, double* sh, int* flag,
-                                              double& total) {
-    if (threadIdx.x == 0) {
-        store_sc1(&partials[blockIdx.x], block_total);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add((gu32*)counter, 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-        *flag = (t == gridDim.x - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (*flag == 0) return false;
-    double s = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += NT) s += load_sc1(&partials[b]);
-    total = block_sum(s, sh);
-    if (threadIdx.x == 0)
-        __hip_atomic_store((gu32*)counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
-
-// Same protocol for NTH-thread workgroups; `sh` needs NTH/64 doubles of LDS
-// that no wave still reads (callers pass their stencil row buffer after the
-// workgroup barrier that ends the sweep).
-template <int NTH>
-__device__ __forceinline__ bool grid_sum_last_n(double block_total, double* partials,
-                                                unsigned* counter, double* sh, int* flag,
-                                                double& total, unsigned pofs = 0,
-                                                unsigned ptot = 0) {
-    if (ptot == 0) ptot = gridDim.x;
-    if (threadIdx.x == 0) {
-        store_sc1(&partials[pofs + blockIdx.x], block_total);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add((gu32*)counter, 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-        *flag = (t == ptot - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (*flag == 0) return false;
-    double s = 0.0;
-    for (unsigned b = threadIdx.x; b < ptot; b += NTH) s += load_sc1(&partials[b]);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-#pragma unroll
-        for (int w = 0; w < NTH / 64; ++w) a += sh[w];
-        total = a;
-        __hip_atomic_store((gu32*)counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return true;
-}
-
-// Order-preserving encoding of doubles into uint64 for atomicMax.
-__device__ __forceinline__ unsigned long long ord_enc(double d) {
-    unsigned long long b = (unsigned long long)__double_as_longlong(d);
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-}
-
-struct TileCoord {
-    int i, j, kb, ke;
-    bool active;
-};
-
-__device__ __forceinline__ TileCoord tile_coord(const Geo& g, int t) {
-    TileCoord c;
-    const int tx = t % g.tiles_x;
-    const int rest = t / g.tiles_x;
-    const int ty = rest % g.tiles_y;
-    const int tz = rest / g.tiles_y;
-    c.i = tx * TX + (threadIdx.x & 63);
-    c.j = ty * TY + (threadIdx.x >> 6);
-    c.kb = g.k0 + tz * g.kc;
-    c.ke = min(c.kb + g.kc, g.k1);
-    c.active = (c.i >= 1) && (c.i <= g.nx - 2) && (c.j >= 1) && (c.j <= g.ny - 2);
-    return c;
-}
-
-__device__ __forceinline__ long long cidx(const Geo& g, int i, int j, int k) {
-    return (long long)k * g.ps + (long long)j * g.px + i;
-}
 
 // Laplacian exactly as linear_solver_cg.c:113-116 groups it.
 __device__ __forceinline__ double lap7(const Lap& L, double c, double xm, double xp, double ym,
@@ -273,8 +87,6 @@ __device__ __forceinline__ void fin_B(CgState* st, double tot, int it) {
         }
     }
 }
-
-constexpr int ST_COMM_TIMEOUT = 9;
 
 __device__ __forceinline__ void comm_fail(CgState* st) {
     st->done = 1;
@@ -380,130 +192,6 @@ static __global__ __launch_bounds__(NT) void k_cg_setup(Geo g, Lap L, DivCoef dc
 // 4.3-4.5 TB/s for one-cell-per-lane designs.
 // ===========================================================================
 // SGeo, the tiling of one launch: tile_plan.hpp
-
-__device__ __forceinline__ int xcd_tile(int b, int nt) {
-    // bijective remap: block b runs on XCD b % 8 (round-robin dispatch);
-    // give each XCD a contiguous range of tiles (speed only, never correctness)
-    const int q = nt / 8, rem = nt % 8;
-    const int x = b % 8, l = b / 8;
-    const int start = x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q;
-    return start + l;
-}
-
-__device__ __forceinline__ double2 ld2(const double* p, long long i) {
-    return *reinterpret_cast<const double2*>(p + i);
-}
-__device__ __forceinline__ void st2(double* p, long long i, double2 v) {
-    *reinterpret_cast<double2*>(p + i) = v;
-}
-
-// Sweep variants (template FL): the SW_* flags of tile_plan.hpp.
-typedef double d2x __attribute__((ext_vector_type(2)));
-template <int FL>
-__device__ __forceinline__ void st2v(double* p, long long i, double2 v) {
-    if (FL & SW_NT_STORE) {
-        d2x w = {v.x, v.y};
-        __builtin_nontemporal_store(w, reinterpret_cast<d2x*>(p + i));
-    } else {
-        *reinterpret_cast<double2*>(p + i) = v;
-    }
-}
-// A 16-B store into one plane through a buffer resource: an offset past the
-// plane's bytes is dropped by the hardware, so a lane (or a step) that must
-// not store passes ST_NOSTORE instead of branching around the store. Every
-// step of a march then issues the same stores, and the compiler's vmcnt
-// counting stays exact (a store under a branch counts as possibly absent, so
-// the wait for a later plane's loads would also wait for that store).
-constexpr int ST_NOSTORE = 0x7ffffff0;
-// AUX: the store's cache-policy bits (2: nt, 16: sc1 write-through)
-template <int AUX>
-__device__ __forceinline__ void st2ba(double* plane_base, long long plane_elems, int boff,
-                                      double2 v) {
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(plane_base, 0, (int)(plane_elems * 8), 0x00020000);
-    const unsigned long long bx = (unsigned long long)__double_as_longlong(v.x);
-    const unsigned long long by = (unsigned long long)__double_as_longlong(v.y);
-    const u4 d = {(unsigned)bx, (unsigned)(bx >> 32), (unsigned)by, (unsigned)(by >> 32)};
-    __builtin_amdgcn_raw_buffer_store_b128(d, rs, boff, 0, AUX);
-}
-template <bool NT>
-__device__ __forceinline__ void st2b(double* plane_base, long long plane_elems, int boff,
-                                     double2 v) {
-    st2ba<NT ? 2 : 0>(plane_base, plane_elems, boff, v);  // aux 2: nt
-}
-
-// The load counterpart of st2b: a 16-B load from one plane through a buffer
-// resource; an offset past the plane (ST_NOSTORE) returns zeros without a
-// memory access, so a lane or step that needs no data issues the same load
-// instead of branching around it (no branch: exact vmcnt counting).
-// AUX: the load's cache-policy bits (2: nt, 16: sc1, which bypasses the L1)
-template <int AUX>
-__device__ __forceinline__ double2 ld2ba(const double* plane_base, long long plane_elems,
-                                         int boff) {
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<double*>(plane_base), 0, (int)(plane_elems * 8), 0x00020000);
-    const u4 d = __builtin_amdgcn_raw_buffer_load_b128(rs, boff, 0, AUX);
-    const unsigned long long bx = (unsigned long long)d.x | ((unsigned long long)d.y << 32);
-    const unsigned long long by = (unsigned long long)d.z | ((unsigned long long)d.w << 32);
-    return make_double2(__longlong_as_double((long long)bx), __longlong_as_double((long long)by));
-}
-template <bool NT = false>
-__device__ __forceinline__ double2 ld2b(const double* plane_base, long long plane_elems, int boff) {
-    return ld2ba<NT ? 2 : 0>(plane_base, plane_elems, boff);  // aux 2: nt
-}
-
-template <int FL>
-__device__ __forceinline__ double2 ld2v(const double* p, long long i) {
-    if (FL & SW_NT_LOAD) {
-        d2x w = __builtin_nontemporal_load(reinterpret_cast<const d2x*>(p + i));
-        return make_double2(w.x, w.y);
-    }
-    return *reinterpret_cast<const double2*>(p + i);
-}
-
-struct RowPair {
-    int i0, j, kb, ke, lane, w;
-    bool act, in0, in1;
-    long long idx;   // cell (i0, clamp(j), kb)
-};
-
-template <int TY>
-__device__ __forceinline__ RowPair row_pair(const SGeo& g) {
-    RowPair c;
-    const int nt = g.tiles_x * g.tiles_y * g.tiles_z;
-    const int t = xcd_tile(blockIdx.x, nt);
-    const int tx = t % g.tiles_x;
-    const int rest = t / g.tiles_x;
-    const int ty = rest % g.tiles_y;
-    const int tz = rest / g.tiles_y;
-    c.lane = threadIdx.x & 63;
-    c.w = threadIdx.x >> 6;
-    c.i0 = tx * 128 + 2 * c.lane;
-    c.j = ty * TY + c.w;
-    if (g.kmode == 1) {
-        c.kb = (tz == 0) ? g.k0 : g.k1 - 1;
-        c.ke = c.kb + 1;
-    } else {
-        c.kb = g.k0 + tz * g.kc;
-        c.ke = min(c.kb + g.kc, g.k1);
-    }
-    c.act = (c.j >= 1) && (c.j <= g.ny - 2) && (c.i0 < g.nx);
-    c.in0 = c.act && (c.i0 >= 1) && (c.i0 <= g.nx - 2);
-    c.in1 = c.act && (c.i0 + 1 <= g.nx - 2);
-    const int ic = min(c.i0, g.nx - 2 - ((g.nx - 2) & 1));  // even, in-row, 16-B aligned
-    const int jc = min(c.j, g.ny - 1);
-    c.idx = (long long)c.kb * g.ps + (long long)jc * g.px + (c.i0 < g.nx ? c.i0 : ic);
-    return c;
-}
-
-// (r01e: asking for 8 waves per SIMD, i.e. <= 64 VGPRs and two 1024-thread
-// workgroups per CU, spills and is slower; profiles/r01e_sweep_variants.jsonl)
-template <int FL>
-constexpr int sweep_min_waves() {
-    return (FL & SW_PREFETCH) ? 4 : 1;
-}
 
 template <bool NT>
 __device__ __forceinline__ double2 ld2n(const double* p, long long i) {
@@ -1327,86 +1015,6 @@ static __global__ __launch_bounds__(64 * TY) void k_cc2(SGeo g, Lap L,
         cc_reduce_finish(st, tg, td, it, INIT, DIST, mb, dsum);
 }
 
-// ---------------------------------------------------------------------------
-// Boundary conditions as pure gathers from interior cells (race-free):
-//   Neumann  (boundary_conditions_core_impl.h:41-85): c -> clamp(c, 1, n-2)
-//   Periodic (:90-134):                               0 -> n-2, n-1 -> 1
-// The reference applies x faces, then y faces, then z faces in place; the
-// composition of those copies is exactly this per-coordinate map, edges and
-// corners included. Dirichlet (:139-186) keeps the z > y > x face precedence.
-// Threads cover the boundary shell: z faces (3-D) plus the x/y ring of every
-// plane. mode: 0 Neumann, 1 periodic, 2 Dirichlet.
-// ---------------------------------------------------------------------------
-struct DirVals {
-    double left, right, top, bottom, front, back;
-};
-
-__device__ __forceinline__ int bc_map(int c, int n, int mode) {
-    if (mode == 0) return c == 0 ? 1 : (c == n - 1 ? n - 2 : c);
-    return c == 0 ? n - 2 : (c == n - 1 ? 1 : c);
-}
-
-// In a Z-slab the z faces exist only on the edge ranks (lo_face / hi_face);
-// the x/y ring is applied on every local plane, halo planes included (their
-// owner applies the identical gather to the same values).
-// Boundary-shell cell e of the enumeration k_bc_shell / k_rx_shell share:
-// the x/y ring of every local plane, then the z faces the rank owns.
-__device__ __forceinline__ long long shell_total(const Geo& g) {
-    const bool is3d = g.nz > 1;
-    const long long ring = 2LL * g.nx + 2LL * (g.ny - 2);
-    const long long plane = (long long)g.nx * g.ny;
-    return ring * g.nz + ((is3d && g.lo_face) ? plane : 0) + ((is3d && g.hi_face) ? plane : 0);
-}
-__device__ __forceinline__ void shell_cell(const Geo& g, long long e, int& i, int& j, int& k,
-                                           bool& zlo, bool& zhi) {
-    const bool is3d = g.nz > 1;
-    const bool lo = is3d && g.lo_face, hi = is3d && g.hi_face;
-    const long long ring = 2LL * g.nx + 2LL * (g.ny - 2);  // x/y boundary ring of one plane
-    const long long nring = ring * g.nz;
-    const long long plane = (long long)g.nx * g.ny;
-    if (e < nring) {
-        k = (int)(e / ring);
-        long long q = e % ring;
-        if (q < g.nx) { i = (int)q; j = 0; }
-        else if (q < 2LL * g.nx) { i = (int)(q - g.nx); j = g.ny - 1; }
-        else if (q < 2LL * g.nx + (g.ny - 2)) { i = 0; j = (int)(q - 2LL * g.nx) + 1; }
-        else { i = g.nx - 1; j = (int)(q - 2LL * g.nx - (g.ny - 2)) + 1; }
-    } else {
-        long long q = e - nring;
-        k = (lo && q < plane) ? 0 : g.nz - 1;
-        q = q % plane;
-        j = (int)(q / g.nx);
-        i = (int)(q % g.nx);
-    }
-    zlo = lo && k == 0;
-    zhi = hi && k == g.nz - 1;
-}
-
-static __global__ __launch_bounds__(256) void k_bc_shell(Geo g, double* __restrict__ f, int mode,
-                                                  DirVals dv) {
-    const long long total = shell_total(g);
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-         e += (long long)gridDim.x * blockDim.x) {
-        int i, j, k;
-        bool zlo, zhi;
-        shell_cell(g, e, i, j, k, zlo, zhi);
-        const long long dst = cidx(g, i, j, k);
-        if (mode == 2) {
-            double v;
-            if (zlo) v = dv.back;
-            else if (zhi) v = dv.front;
-            else if (j == 0) v = dv.bottom;
-            else if (j == g.ny - 1) v = dv.top;
-            else if (i == 0) v = dv.left;
-            else v = dv.right;
-            f[dst] = v;
-        } else {
-            int si = bc_map(i, g.nx, mode), sj = bc_map(j, g.ny, mode);
-            int sk = (zlo || zhi) ? bc_map(k, g.nz, mode) : k;
-            f[dst] = f[cidx(g, si, sj, sk)];
-        }
-    }
-}
 
 // Max over a full field (stats: max temperature, solver_registry.c:52-62),
 // planes [k_first, k_first + gridDim.z).
@@ -1535,1297 +1143,6 @@ static __global__ __launch_bounds__(256) void k_thermal_bc(Geo g, double* __rest
     }
 }
 
-// ---------------------------------------------------------------------------
-// RK4 (solver_rk4.c:69-259) with the shared momentum RHS
-// (ns_momentum_rhs_scalar.h:49-190). One fused kernel per stage s:
-//   k      = RHS(cur)                      (interior; 0 on boundary cells)
-//   acc    = k | acc + 2k | acc + 2k       (s = 0, 1, 2: the reference's
-//                                           k1 + 2 k2 + 2 k3 + k4, left to right)
-//   out    = clamp(Q0 + fac_s k)           (s < 3; fac = dt/2, dt/2, dt)
-//   out    = clamp(Q0 + dt/6 (acc + k))    (s = 3, written in place over Q0)
-// so the stage derivatives never touch HBM. The stencil uses the
-// reference's periodic neighbour indices (i = 1 reads nx-2, not the ghost).
-// ---------------------------------------------------------------------------
-struct RkCoef {
-    double inv_2dz, inv_dz2;
-    double mu, beta, T_ref, g0, g1, g2;
-    double fac;   // dt/2, dt/2, dt, dt/6
-};
-
-struct Fld4 {
-    double* f[4];  // u, v, w, p
-};
-
-__device__ __forceinline__ double clampl(double x, double lim) { return fmax(-lim, fmin(lim, x)); }
-
-// One cell's RHS (ns_momentum_rhs_scalar.h:49-190 operation order): the 7
-// values of u, v, w, p around the cell (periodic neighbour indices already
-// resolved), rho, dx[i], dy[j], the source-table entries and T; kr = 0 where
-// the reference skips the cell (rho or a spacing below 1e-10).
-struct RkNbr {
-    double c[4], l[4], r[4], d[4], u[4], m[4], p[4];  // centre, x-, x+, y-, y+, z-, z+
-};
-
-template <bool BUOY>
-__device__ __forceinline__ void rk_rhs(const RkCoef& rc, const RkNbr& n, double r, double dxi,
-                                       double dyj, double su, double sv, double Tc,
-                                       double (&kr)[4]) {
-    if (!(r <= 1e-10) && !(fabs(dxi) < 1e-10) && !(fabs(dyj) < 1e-10)) {
-        const double tdx = 2.0 * dxi, tdy = 2.0 * dyj;
-        const double dxx = dxi * dxi, dyy = dyj * dyj;
-        const double uc = n.c[0], vc = n.c[1], wc = n.c[2];
-        double du_dx = (n.r[0] - n.l[0]) / tdx, du_dy = (n.u[0] - n.d[0]) / tdy;
-        double du_dz = (n.p[0] - n.m[0]) * rc.inv_2dz;
-        double dv_dx = (n.r[1] - n.l[1]) / tdx, dv_dy = (n.u[1] - n.d[1]) / tdy;
-        double dv_dz = (n.p[1] - n.m[1]) * rc.inv_2dz;
-        double dw_dx = (n.r[2] - n.l[2]) / tdx, dw_dy = (n.u[2] - n.d[2]) / tdy;
-        double dw_dz = (n.p[2] - n.m[2]) * rc.inv_2dz;
-        double dp_dx = (n.r[3] - n.l[3]) / tdx, dp_dy = (n.u[3] - n.d[3]) / tdy;
-        double dp_dz = (n.p[3] - n.m[3]) * rc.inv_2dz;
-        double d2u_dx2 = (n.r[0] - 2.0 * uc + n.l[0]) / dxx;
-        double d2u_dy2 = (n.u[0] - 2.0 * uc + n.d[0]) / dyy;
-        double d2u_dz2 = (n.p[0] - 2.0 * uc + n.m[0]) * rc.inv_dz2;
-        double d2v_dx2 = (n.r[1] - 2.0 * vc + n.l[1]) / dxx;
-        double d2v_dy2 = (n.u[1] - 2.0 * vc + n.d[1]) / dyy;
-        double d2v_dz2 = (n.p[1] - 2.0 * vc + n.m[1]) * rc.inv_dz2;
-        double d2w_dx2 = (n.r[2] - 2.0 * wc + n.l[2]) / dxx;
-        double d2w_dy2 = (n.u[2] - 2.0 * wc + n.d[2]) / dyy;
-        double d2w_dz2 = (n.p[2] - 2.0 * wc + n.m[2]) * rc.inv_dz2;
-        double nu = rc.mu / fmax(r, 1e-10);
-        nu = fmin(nu, 1.0);
-        du_dx = clampl(du_dx, 100.0); du_dy = clampl(du_dy, 100.0); du_dz = clampl(du_dz, 100.0);
-        dv_dx = clampl(dv_dx, 100.0); dv_dy = clampl(dv_dy, 100.0); dv_dz = clampl(dv_dz, 100.0);
-        dw_dx = clampl(dw_dx, 100.0); dw_dy = clampl(dw_dy, 100.0); dw_dz = clampl(dw_dz, 100.0);
-        dp_dx = clampl(dp_dx, 100.0); dp_dy = clampl(dp_dy, 100.0); dp_dz = clampl(dp_dz, 100.0);
-        d2u_dx2 = clampl(d2u_dx2, 1000.0); d2u_dy2 = clampl(d2u_dy2, 1000.0);
-        d2u_dz2 = clampl(d2u_dz2, 1000.0); d2v_dx2 = clampl(d2v_dx2, 1000.0);
-        d2v_dy2 = clampl(d2v_dy2, 1000.0); d2v_dz2 = clampl(d2v_dz2, 1000.0);
-        d2w_dx2 = clampl(d2w_dx2, 1000.0); d2w_dy2 = clampl(d2w_dy2, 1000.0);
-        d2w_dz2 = clampl(d2w_dz2, 1000.0);
-        double sw = 0.0;
-        if (BUOY) {
-            const double dT = Tc - rc.T_ref;
-            su += -rc.beta * dT * rc.g0;
-            sv += -rc.beta * dT * rc.g1;
-            sw += -rc.beta * dT * rc.g2;
-        }
-        kr[0] = -uc * du_dx - vc * du_dy - wc * du_dz - dp_dx / r +
-                nu * (d2u_dx2 + d2u_dy2 + d2u_dz2) + su;
-        kr[1] = -uc * dv_dx - vc * dv_dy - wc * dv_dz - dp_dy / r +
-                nu * (d2v_dx2 + d2v_dy2 + d2v_dz2) + sv;
-        kr[2] = -uc * dw_dx - vc * dw_dy - wc * dw_dz - dp_dz / r +
-                nu * (d2w_dx2 + d2w_dy2 + d2w_dz2) + sw;
-        double div = du_dx + dv_dy + dw_dz;
-        div = fmax(-10.0, fmin(10.0, div));
-        kr[3] = -0.1 * r * div;
-    }
-}
-
-template <int STAGE, bool BUOY>
-__global__ __launch_bounds__(256) void k_rk_stage(Geo g, RkCoef rc, Fld4 cur, Fld4 q0, Fld4 acc,
-                                                  Fld4 out, const double* __restrict__ rho,
-                                                  const double* __restrict__ T,
-                                                  const double* __restrict__ dxa,
-                                                  const double* __restrict__ dya,
-                                                  const double* __restrict__ su_row,
-                                                  const double* __restrict__ sv_col) {
-    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int k = blockIdx.z;
-    if (i >= g.nx || j >= g.ny) return;
-    const long long idx = cidx(g, i, j, k);
-    const bool interior = (i >= 1 && i <= g.nx - 2 && j >= 1 && j <= g.ny - 2 &&
-                           k >= g.k0 && k < g.k1);
-    double kr[4] = {0.0, 0.0, 0.0, 0.0};
-    if (interior) {
-        const long long il = (i > 1) ? idx - 1 : cidx(g, g.nx - 2, j, k);
-        const long long ir = (i < g.nx - 2) ? idx + 1 : cidx(g, 1, j, k);
-        const long long jd = (j > 1) ? idx - g.px : cidx(g, i, g.ny - 2, k);
-        const long long ju = (j < g.ny - 2) ? idx + g.px : cidx(g, i, 1, k);
-        long long kd = idx, ku = idx;   // 2-D: z terms vanish (stride 0)
-        if (g.sz) {
-            kd = (k > 1) ? idx - g.sz : cidx(g, i, j, g.nz - 2);
-            ku = (k < g.nz - 2) ? idx + g.sz : cidx(g, i, j, 1);
-        }
-        RkNbr n;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            n.c[f] = cur.f[f][idx];
-            n.l[f] = cur.f[f][il];
-            n.r[f] = cur.f[f][ir];
-            n.d[f] = cur.f[f][jd];
-            n.u[f] = cur.f[f][ju];
-            n.m[f] = cur.f[f][kd];
-            n.p[f] = cur.f[f][ku];
-        }
-        rk_rhs<BUOY>(rc, n, rho[idx], dxa[i], dya[j], su_row[j], sv_col[i],
-                     BUOY ? T[idx] : 0.0, kr);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double o;
-        if (STAGE == 0) {
-            acc.f[q][idx] = kr[q];
-            o = q0.f[q][idx] + rc.fac * kr[q];
-        } else if (STAGE < 3) {
-            acc.f[q][idx] = acc.f[q][idx] + 2.0 * kr[q];
-            o = q0.f[q][idx] + rc.fac * kr[q];
-        } else {
-            o = q0.f[q][idx] + rc.fac * (acc.f[q][idx] + kr[q]);
-        }
-        if (q < 3) o = fmax(-100.0, fmin(100.0, o));
-        out.f[q][idx] = o;
-    }
-}
-
-// First and second differences of one field at the cells (i0, i0 + 1) of a
-// pair (r02b): c2 the pair, d2 / u2 the
-// (periodically resolved) y- / y+ rows, m2 / p2 the z- / z+ planes, xl the
-// left of i0, ar the right of i0, bl the left of i0 + 1, xr the right of
-// i0 + 1. Same expressions and order as rk_rhs, so the values are bitwise.
-struct RkD1 {
-    double dx, dy, dz, xx, yy, zz;
-};
-
-__device__ __forceinline__ void rk_pair_diffs(const RkCoef& rc, double2 c2, double2 d2, double2 u2,
-                                              double2 m2, double2 p2, double xl, double ar,
-                                              double bl, double xr, double dxa0, double dxa1,
-                                              double dyj, RkD1& da, RkD1& db) {
-    const double tdxa = 2.0 * dxa0, tdxb = 2.0 * dxa1, tdy = 2.0 * dyj;
-    const double dxxa = dxa0 * dxa0, dxxb = dxa1 * dxa1, dyy = dyj * dyj;
-    da.dx = (ar - xl) / tdxa;
-    da.dy = (u2.x - d2.x) / tdy;
-    da.dz = (p2.x - m2.x) * rc.inv_2dz;
-    da.xx = (ar - 2.0 * c2.x + xl) / dxxa;
-    da.yy = (u2.x - 2.0 * c2.x + d2.x) / dyy;
-    da.zz = (p2.x - 2.0 * c2.x + m2.x) * rc.inv_dz2;
-    db.dx = (xr - bl) / tdxb;
-    db.dy = (u2.y - d2.y) / tdy;
-    db.dz = (p2.y - m2.y) * rc.inv_2dz;
-    db.xx = (xr - 2.0 * c2.y + bl) / dxxb;
-    db.yy = (u2.y - 2.0 * c2.y + d2.y) / dyy;
-    db.zz = (p2.y - 2.0 * c2.y + m2.y) * rc.inv_dz2;
-}
-
-// The stage derivatives of a pair (rk_rhs's expressions): diffs(f, da, db)
-// yields field f's differences; p first (its gradient enters u, v, w), then
-// u, v, w, so only one field's neighbourhood is live at a time.
-template <bool BUOY, class Diffs>
-__device__ __forceinline__ void rk_pair_kr(const RkCoef& rc, Diffs diffs, double2 uc, double2 vc,
-                                           double2 wc, double2 r2, double2 t2, double su,
-                                           double sv0, double sv1, bool oka, bool okb,
-                                           double (&kra)[4], double (&krb)[4],
-                                           double* div2 = nullptr) {
-    RkD1 pa_, pb_;
-    diffs(3, pa_, pb_);
-    const double dpxa = clampl(pa_.dx, 100.0), dpya = clampl(pa_.dy, 100.0),
-                 dpza = clampl(pa_.dz, 100.0);
-    const double dpxb = clampl(pb_.dx, 100.0), dpyb = clampl(pb_.dy, 100.0),
-                 dpzb = clampl(pb_.dz, 100.0);
-    const double nua = fmin(rc.mu / fmax(r2.x, 1e-10), 1.0);
-    const double nub = fmin(rc.mu / fmax(r2.y, 1e-10), 1.0);
-    double sa[3] = {su, sv0, 0.0};
-    double sb[3] = {su, sv1, 0.0};
-    if (BUOY) {
-        const double dTa = t2.x - rc.T_ref, dTb = t2.y - rc.T_ref;
-        sa[0] += -rc.beta * dTa * rc.g0;
-        sa[1] += -rc.beta * dTa * rc.g1;
-        sa[2] += -rc.beta * dTa * rc.g2;
-        sb[0] += -rc.beta * dTb * rc.g0;
-        sb[1] += -rc.beta * dTb * rc.g1;
-        sb[2] += -rc.beta * dTb * rc.g2;
-    }
-    const double gpa[3] = {dpxa, dpya, dpza}, gpb[3] = {dpxb, dpyb, dpzb};
-    double diva = 0.0, divb = 0.0;  // du_dx + dv_dy + dw_dz (clamped terms)
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-        RkD1 da, db;
-        diffs(f, da, db);
-        da.dx = clampl(da.dx, 100.0); da.dy = clampl(da.dy, 100.0); da.dz = clampl(da.dz, 100.0);
-        db.dx = clampl(db.dx, 100.0); db.dy = clampl(db.dy, 100.0); db.dz = clampl(db.dz, 100.0);
-        da.xx = clampl(da.xx, 1000.0); da.yy = clampl(da.yy, 1000.0); da.zz = clampl(da.zz, 1000.0);
-        db.xx = clampl(db.xx, 1000.0); db.yy = clampl(db.yy, 1000.0); db.zz = clampl(db.zz, 1000.0);
-        if (oka)
-            kra[f] = -uc.x * da.dx - vc.x * da.dy - wc.x * da.dz - gpa[f] / r2.x +
-                     nua * (da.xx + da.yy + da.zz) + sa[f];
-        if (okb)
-            krb[f] = -uc.y * db.dx - vc.y * db.dy - wc.y * db.dz - gpb[f] / r2.y +
-                     nub * (db.xx + db.yy + db.zz) + sb[f];
-        const double ta = (f == 0) ? da.dx : (f == 1 ? da.dy : da.dz);
-        const double tb = (f == 0) ? db.dx : (f == 1 ? db.dy : db.dz);
-        diva = (f == 0) ? ta : diva + ta;
-        divb = (f == 0) ? tb : divb + tb;
-    }
-    if (oka) kra[3] = -0.1 * r2.x * fmax(-10.0, fmin(10.0, diva));
-    if (okb) krb[3] = -0.1 * r2.y * fmax(-10.0, fmin(10.0, divb));
-    if (div2) {  // the clamped divergence itself (k_euler_step scales it by dt)
-        div2[0] = fmax(-10.0, fmin(10.0, diva));
-        div2[1] = fmax(-10.0, fmin(10.0, divb));
-    }
-}
-
-// The stage update of one pair of field q (solver_rk4.c stage sums): stage
-// 0 stores k into the running sum, 1-2 add 2k, 3 forms the final state.
-template <int STAGE, int FL = 0>
-__device__ __forceinline__ void rk_pair_update(const RkCoef& rc, const Fld4& q0, const Fld4& acc,
-                                               const Fld4& out, int q, long long idx, double ka,
-                                               double kb) {
-    const double2 q02 = ld2v<FL>(q0.f[q], idx);
-    double2 o;
-    if (STAGE == 0) {
-        st2v<FL>(acc.f[q], idx, make_double2(ka, kb));
-        o = make_double2(q02.x + rc.fac * ka, q02.y + rc.fac * kb);
-    } else if (STAGE < 3) {
-        const double2 a2 = ld2v<FL>(acc.f[q], idx);
-        st2v<FL>(acc.f[q], idx, make_double2(a2.x + 2.0 * ka, a2.y + 2.0 * kb));
-        o = make_double2(q02.x + rc.fac * ka, q02.y + rc.fac * kb);
-    } else {
-        const double2 a2 = ld2v<FL>(acc.f[q], idx);
-        o = make_double2(q02.x + rc.fac * (a2.x + ka), q02.y + rc.fac * (a2.y + kb));
-    }
-    if (q < 3) {
-        o.x = fmax(-100.0, fmin(100.0, o.x));
-        o.y = fmax(-100.0, fmin(100.0, o.y));
-    }
-    st2v<FL>(out.f[q], idx, o);
-}
-
-// The same stage on x pairs (r02b): each lane owns cells (i0, i0 + 1) and
-// moves every field with 16-B loads / stores; the cell's x neighbours are the
-// pair's other cell or one scalar load (the periodic indices of i = 1 and
-// nx - 2 by address), y / z neighbours are pair loads of the (periodically
-// resolved) neighbour row / plane. Half the load instructions of k_rk_stage;
-// rk_rhs's expressions, so the values are bitwise the per-cell kernel's.
-template <int STAGE, bool BUOY>
-__global__ __launch_bounds__(256) void k_rk_stage2(Geo g, RkCoef rc, Fld4 cur, Fld4 q0, Fld4 acc,
-                                                   Fld4 out, const double* __restrict__ rho,
-                                                   const double* __restrict__ T,
-                                                   const double* __restrict__ dxa,
-                                                   const double* __restrict__ dya,
-                                                   const double* __restrict__ su_row,
-                                                   const double* __restrict__ sv_col) {
-    const int i0 = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
-    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int k = blockIdx.z;
-    if (i0 >= g.nx || j >= g.ny) return;
-    const long long idx = cidx(g, i0, j, k);
-    const bool rowin = (j >= 1 && j <= g.ny - 2 && k >= g.k0 && k < g.k1);
-    const bool ina = rowin && i0 >= 1 && i0 <= g.nx - 2;
-    const bool inb = rowin && i0 + 1 <= g.nx - 2;
-    double kra[4] = {0.0, 0.0, 0.0, 0.0}, krb[4] = {0.0, 0.0, 0.0, 0.0};
-    if (ina || inb) {
-        const long long row = idx - i0;
-        const long long jd = (j > 1) ? idx - g.px : cidx(g, i0, g.ny - 2, k);
-        const long long ju = (j < g.ny - 2) ? idx + g.px : cidx(g, i0, 1, k);
-        long long kd = idx, ku = idx;  // 2-D: z terms vanish (stride 0)
-        if (g.sz) {
-            kd = (k > 1) ? idx - g.sz : cidx(g, i0, j, g.nz - 2);
-            ku = (k < g.nz - 2) ? idx + g.sz : cidx(g, i0, j, 1);
-        }
-        // x neighbours outside the pair: left of i0, right of i0 + 1
-        const long long la = (i0 > 1) ? idx - 1 : row + (g.nx - 2);
-        const long long rb = (i0 + 1 < g.nx - 2) ? idx + 2 : row + 1;
-        const double2 r2 = ld2(rho, idx);
-        const double2 t2 = BUOY ? ld2(T, idx) : make_double2(0.0, 0.0);
-        const double dyj = dya[j], su = su_row[j];
-        const double dxa0 = dxa[i0], dxa1 = dxa[min(i0 + 1, g.nx - 1)];
-        const bool oka = ina && !(r2.x <= 1e-10) && !(fabs(dxa0) < 1e-10) && !(fabs(dyj) < 1e-10);
-        const bool okb = inb && !(r2.y <= 1e-10) && !(fabs(dxa1) < 1e-10) && !(fabs(dyj) < 1e-10);
-        const double2 uc = ld2(cur.f[0], idx), vc = ld2(cur.f[1], idx), wc = ld2(cur.f[2], idx);
-        auto diffs = [&](int f, RkD1& da, RkD1& db) __attribute__((always_inline)) {
-            const double* F = cur.f[f];
-            const double2 c2 = ld2(F, idx), d2 = ld2(F, jd), u2 = ld2(F, ju);
-            const double2 m2 = ld2(F, kd), p2 = ld2(F, ku);
-            const double xl = F[la], xr = F[rb];
-            const double ar = (i0 < g.nx - 2) ? c2.y : F[row + 1];
-            const double bl = (i0 + 1 > 1) ? c2.x : F[row + (g.nx - 2)];
-            rk_pair_diffs(rc, c2, d2, u2, m2, p2, xl, ar, bl, xr, dxa0, dxa1, dyj, da, db);
-        };
-        rk_pair_kr<BUOY>(rc, diffs, uc, vc, wc, r2, t2, su, sv_col[i0],
-                         sv_col[min(i0 + 1, g.nx - 1)], oka, okb, kra, krb);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rk_pair_update<STAGE>(rc, q0, acc, out, q, idx, kra[q], krb[q]);
-}
-
-// ---------------------------------------------------------------------------
-// Explicit Euler (solver_explicit_euler.c:391-525): the whole update of u, v,
-// w, p in one pass on k_rk_stage2's x pairs (128 columns x 4 rows per
-// workgroup, 16-B loads and stores). The momentum expressions are the RK
-// RHS's (rk_pair_kr); what differs from an RK stage:
-//   - the stencil reads the ghost cells: neighbours are idx +- 1, +- px,
-//     +- sz by address, no periodic index resolution (2-D: sz = 0);
-//   - the increments rc.fac * k (rc.fac = min(dt, 1e-4)) are clamped to +-1
-//     before they are added, u, v, w then to +-100;
-//   - dp = -0.1 * fac * rho * clamp(div, +-10), clamped to +-1;
-//   - boundary cells and the cells the reference skips (rho <= 1e-10 or a
-//     spacing below 1e-10) keep their values: every cell of `out` is written,
-//     so the caller swaps cur and out.
-// Per cell: reads u, v, w, p, rho (and T with buoyancy), writes u, v, w, p:
-// 72 / 80 B of algorithmic traffic.
-// ---------------------------------------------------------------------------
-template <bool BUOY>
-__global__ __launch_bounds__(256) void k_euler_step(Geo g, RkCoef rc, Fld4 cur, Fld4 out,
-                                                    const double* __restrict__ rho,
-                                                    const double* __restrict__ T,
-                                                    const double* __restrict__ dxa,
-                                                    const double* __restrict__ dya,
-                                                    const double* __restrict__ su_row,
-                                                    const double* __restrict__ sv_col) {
-    const int i0 = blockIdx.x * 128 + 2 * (threadIdx.x & 63);
-    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int k = blockIdx.z;
-    if (i0 >= g.nx || j >= g.ny) return;
-    const long long idx = cidx(g, i0, j, k);
-    const bool rowin = (j >= 1 && j <= g.ny - 2 && k >= g.k0 && k < g.k1);
-    const bool ina = rowin && i0 >= 1 && i0 <= g.nx - 2;
-    const bool inb = rowin && i0 + 1 <= g.nx - 2;
-    double2 o[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) o[q] = ld2(cur.f[q], idx);
-    if (ina || inb) {
-        const long long jd = idx - g.px, ju = idx + g.px;
-        const long long kd = idx - g.sz, ku = idx + g.sz;  // 2-D: sz = 0, z terms vanish
-        const double2 r2 = ld2(rho, idx);
-        const double2 t2 = BUOY ? ld2(T, idx) : make_double2(0.0, 0.0);
-        const double dyj = dya[j], su = su_row[j];
-        const double dxa0 = dxa[i0], dxa1 = dxa[min(i0 + 1, g.nx - 1)];
-        const bool oka = ina && !(r2.x <= 1e-10) && !(fabs(dxa0) < 1e-10) && !(fabs(dyj) < 1e-10);
-        const bool okb = inb && !(r2.y <= 1e-10) && !(fabs(dxa1) < 1e-10) && !(fabs(dyj) < 1e-10);
-        auto diffs = [&](int f, RkD1& da, RkD1& db) __attribute__((always_inline)) {
-            const double* F = cur.f[f];
-            const double2 c2 = ld2(F, idx), d2 = ld2(F, jd), u2 = ld2(F, ju);
-            const double2 m2 = ld2(F, kd), p2 = ld2(F, ku);
-            // x neighbours outside the pair; a cell that needs one is interior,
-            // so i0 - 1 >= 0 and i0 + 2 <= nx - 1 where the value is used
-            const double xl = ina ? F[idx - 1] : 0.0;
-            const double xr = inb ? F[idx + 2] : 0.0;
-            rk_pair_diffs(rc, c2, d2, u2, m2, p2, xl, c2.y, c2.x, xr, dxa0, dxa1, dyj, da, db);
-        };
-        double kra[4] = {0.0, 0.0, 0.0, 0.0}, krb[4] = {0.0, 0.0, 0.0, 0.0};
-        double div2[2] = {0.0, 0.0};
-        rk_pair_kr<BUOY>(rc, diffs, o[0], o[1], o[2], r2, t2, su, sv_col[i0],
-                         sv_col[min(i0 + 1, g.nx - 1)], oka, okb, kra, krb, div2);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            if (oka) o[q].x = clampl(o[q].x + clampl(rc.fac * kra[q], 1.0), 100.0);
-            if (okb) o[q].y = clampl(o[q].y + clampl(rc.fac * krb[q], 1.0), 100.0);
-        }
-        if (oka) o[3].x = o[3].x + clampl(-0.1 * rc.fac * r2.x * div2[0], 1.0);
-        if (okb) o[3].y = o[3].y + clampl(-0.1 * rc.fac * r2.y * div2[1], 1.0);
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) st2(out.f[q], idx, o[q]);
-}
-
-// max |u|, max |p| and the non-finite flag over the owned planes (the
-// stats / NaN scan of the RK wrappers, solver_registry.c:31-49,760-768)
-static __global__ __launch_bounds__(256) void k_vel_stats(Geo g, const double* __restrict__ U,
-                                                          const double* __restrict__ V,
-                                                          const double* __restrict__ W,
-                                                          const double* __restrict__ P,
-                                                          unsigned long long* red) {
-    __shared__ double shv[4], shp[4];
-    __shared__ int shbad;
-    if (threadIdx.x == 0) shbad = 0;
-    __syncthreads();
-    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int k = blockIdx.z;
-    double mv = 0.0, mp = 0.0;
-    if (i < g.nx && j < g.ny) {
-        const long long idx = cidx(g, i, j, k);
-        const double u = U[idx], v = V[idx], w = W[idx], p = P[idx];
-        if (!isfinite(u) || !isfinite(v) || !isfinite(w) || !isfinite(p)) shbad = 1;
-        const double vel2 = (u * u) + (v * v) + (w * w);  // sqrt on the host (cell_stats)
-        if (vel2 > mv) mv = vel2;
-        const double ap = fabs(p);
-        if (ap > mp) mp = ap;
-    }
-    mv = wave_max(mv);
-    mp = wave_max(mp);
-    if ((threadIdx.x & 63) == 0) {
-        shv[threadIdx.x >> 6] = mv;
-        shp[threadIdx.x >> 6] = mp;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        atomicMax(&red[0], ord_enc(fmax(fmax(shv[0], shv[1]), fmax(shv[2], shv[3]))));
-        atomicMax(&red[1], ord_enc(fmax(fmax(shp[0], shp[1]), fmax(shp[2], shp[3]))));
-        if (shbad) atomicOr(&red[2], 1ull);
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Relaxation solvers.
-// Red-Black SOR colour pass (linear_solver_redblack.c:97-133). `parity` is the
-// (i+j+k) parity updated in this pass: the reference's first ("red") pass
-// updates odd cells, the second even cells. Each cell reads only the other
-// colour, so the in-place update is race-free and bitwise the reference's.
-// Jacobi (linear_solver_jacobi.c:92-109) reads xin, writes xout.
-// ---------------------------------------------------------------------------
-struct RelaxCoef {
-    double dx2, dy2, inv_dz2, inv_factor, omega;
-    double rdx2, rdy2;  // RN(1 / dx2), RN(1 / dy2) for divc
-};
-
-// a / d, correctly rounded, for the constant divisors dx2 / dy2 of the
-// relaxation sweeps, from the correctly rounded reciprocal r = RN(1/d):
-// q = RN(a r) is within 1 ulp of a/d, a - q d is exact in one FMA, and the
-// corrected q + (a - q d) r rounds to RN(a/d) (Markstein's correction, the
-// IA-64 division scheme) -- 3 VALU ops instead of the ~14-op generic fp64
-// division, bitwise the reference's `/` (checked on 9.6e8 random quotients,
-// tools/divc_check.c, and by the bitwise relaxation tests). Quotients near the
-// underflow/overflow range, zeros (sign of zero) and non-finite values take
-// the generic division.
-__device__ __forceinline__ double divc(double a, double d, double r) {
-    const double q = a * r;
-    const double aq = fabs(q);
-    if (!(aq >= 0x1p-900 && aq <= 0x1p+900)) return a / d;  // residual stays normal
-    return fma(fma(-q, d, a), r, q);
-}
-
-// Division functors for the stencil helpers. DivC: divc, its range test a
-// branch per division. DivFastZ (below, with divz) defers the test: the fast
-// quotient's range check goes into a lane flag (compare masks, no branch) and
-// the caller recomputes the lanes whose flag dropped with DivExact behind ONE
-// wave-uniform branch; where the flag held the value is divz's, so results
-// are bitwise either way. That form helps the predictor (fewer, longer basic
-// blocks) but spilled in k_rb1 and made it slower (0.845 vs 0.751 ms at
-// 512^3, profiles/r02_deferred_div.jsonl), which keeps DivC.
-struct DivC {  // divc, its range test branching per division
-    __device__ __forceinline__ double operator()(double a, double d, double r) const {
-        return divc(a, d, r);
-    }
-};
-struct DivExact {  // the reference's division (the recompute path)
-    __device__ __forceinline__ double operator()(double a, double d, double) const { return a / d; }
-};
-// true when some lane of the wave dropped its flag (wave-uniform)
-__device__ __forceinline__ bool wave_any_bad(bool ok) {
-    return __builtin_amdgcn_ballot_w64(!ok) != 0;
-}
-
-static __global__ __launch_bounds__(NT) void k_rb_pass(Geo g, RelaxCoef rc, double* __restrict__ x,
-                                                const double* __restrict__ rhs, int parity) {
-    const int ntiles = g.tiles_x * g.tiles_y * g.tiles_z;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        TileCoord c = tile_coord(g, t);
-        if (!c.active) continue;
-        long long idx = cidx(g, c.i, c.j, c.kb);
-        for (int k = c.kb; k < c.ke; ++k, idx += g.ps) {
-            if (((c.i + c.j + k + g.kofs) & 1) != parity) continue;  // global parity
-            double pn = -(rhs[idx] - (x[idx + 1] + x[idx - 1]) / rc.dx2 -
-                          (x[idx + g.px] + x[idx - g.px]) / rc.dy2 -
-                          (x[idx + g.sz] + x[idx - g.sz]) * rc.inv_dz2) *
-                        rc.inv_factor;
-            double xo = x[idx];
-            x[idx] = xo + rc.omega * (pn - xo);
-        }
-    }
-}
-
-static __global__ __launch_bounds__(NT) void k_jacobi(Geo g, RelaxCoef rc, const double* __restrict__ xin,
-                                               double* __restrict__ xout,
-                                               const double* __restrict__ rhs) {
-    const int ntiles = g.tiles_x * g.tiles_y * g.tiles_z;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        TileCoord c = tile_coord(g, t);
-        if (!c.active) continue;
-        long long idx = cidx(g, c.i, c.j, c.kb);
-        for (int k = c.kb; k < c.ke; ++k, idx += g.ps) {
-            xout[idx] = -(rhs[idx] - (xin[idx + 1] + xin[idx - 1]) / rc.dx2 -
-                          (xin[idx + g.px] + xin[idx - g.px]) / rc.dy2 -
-                          (xin[idx + g.sz] + xin[idx - g.sz]) * rc.inv_dz2) *
-                         rc.inv_factor;
-        }
-    }
-}
-
-// L-infinity residual |lap(x) - rhs| (linear_solver.c:304-346, division form).
-struct ResCoef {
-    double dx2, dy2, inv_dz2;
-};
-
-static __global__ __launch_bounds__(NT) void k_residual_linf(Geo g, ResCoef rc,
-                                                      const double* __restrict__ x,
-                                                      const double* __restrict__ rhs,
-                                                      unsigned long long* out) {
-    __shared__ double sh[NWAVE];
-    double m = 0.0;
-    const int ntiles = g.tiles_x * g.tiles_y * g.tiles_z;
-    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        TileCoord c = tile_coord(g, t);
-        if (!c.active) continue;
-        long long idx = cidx(g, c.i, c.j, c.kb);
-        for (int k = c.kb; k < c.ke; ++k, idx += g.ps) {
-            double lap = (x[idx + 1] - 2.0 * x[idx] + x[idx - 1]) / rc.dx2 +
-                         (x[idx + g.px] - 2.0 * x[idx] + x[idx - g.px]) / rc.dy2 +
-                         (x[idx + g.sz] + x[idx - g.sz] - 2.0 * x[idx]) * rc.inv_dz2;
-            double res = fabs(lap - rhs[idx]);
-            if (res > m) m = res;
-        }
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = sh[0];
-        for (int w = 1; w < NWAVE; ++w) a = fmax(a, sh[w]);
-        atomicMax(out, ord_enc(a));
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Relaxation iterations on the row-pair sweep tiling (single device), with
-// the common loop's convergence test (linear_solver.c:397-485) on the device.
-// Ping-pong buffers: iteration it reads X = buf[it & 1] (the iterate after
-// it - 1 iterations, BCs applied) and leaves buf[(it + 1) & 1].
-//   RB-SOR:  k_rx<RX_RED>   X -> Y: first-colour ((i+j+k) odd, the CPU
-//                           reference's "red", linear_solver_redblack.c:97-114)
-//                           cells SOR-updated, the other cells copied; and the
-//                           L-inf residual of X;
-//            k_rx_shell     boundary shell X -> Y (the sweeps read it);
-//            k_rx<RX_BLACK> Y in place: second-colour cells (:116-133);
-//            k_rx_shell     Neumann BC on Y (poisson_solver_apply_bc).
-//   Jacobi:  k_rx<RX_JACOBI> X -> Y (linear_solver_jacobi.c:92-109) + the
-//            residual of X; k_rx_shell Neumann on Y.
-// The residual of the iterate after iteration it - 1 is thus computed by the
-// first sweep of iteration it, which has to read X anyway (16 B/cell of the
-// reference's separate residual pass saved); when it shows convergence the
-// result is X, still intact in its buffer, and everything launched after it
-// returns at once (RxState.done). Per-cell arithmetic is the reference's, and
-// L-inf (a max) is order-independent, so iterates, residuals and iteration
-// counts are bitwise the reference's.
-// ---------------------------------------------------------------------------
-struct RxState {
-    double tol, abs_tol, rel_tol, res0, res;
-    int iterations, done, status, max_iter, check_interval, result;  // result: buffer index
-    // two iterations per sweep (k_rb2, rb2.hpp): the iterate index the loop
-    // stopped on, whether `res` is that iterate's exact residual, the
-    // host-resolved exact residual of iterate ovr_it (-1: none), and max |rhs|
-    int res_it, res_exact, ovr_it, pad0;
-    double ovr_m, bmax;
-    double xmax;  // max |X| of a k_rb2 sweep's input when it certifies X (k_rb2_xmax)
-};
-
-constexpr int RX_RED = 0;
-constexpr int RX_BLACK = 1;
-constexpr int RX_JACOBI = 2;
-
-// m = L-inf residual of the iterate after it - 1 iterations (it = 0: x0)
-__device__ __forceinline__ void rx_finish(RxState* st, double m, int it) {
-    if (it == 0) {  // linear_solver.c:415-437
-        st->res0 = m;
-        st->res = m;
-        double tol = st->rel_tol * m;
-        if (tol < st->abs_tol) tol = st->abs_tol;
-        st->tol = tol;
-        if (m < st->abs_tol) {
-            st->done = 1;
-            st->status = ST_CONVERGED;
-            st->iterations = 0;
-            st->result = 0;
-            st->res_it = 0;
-        }
-        return;
-    }
-    const int prev = it - 1;  // :443-468, iteration prev just completed
-    if (prev % st->check_interval == 0) {
-        st->res = m;
-        if (m < st->tol || m < st->abs_tol) {
-            st->done = 1;
-            st->status = ST_CONVERGED;
-            st->iterations = it;  // iter + 1 at the break
-            st->result = it & 1;
-            st->res_it = it;
-            return;
-        }
-    }
-    if (it >= st->max_iter) {  // loop ran out: iterations = iter + 1 = max_iter + 1 (:472)
-        st->done = 1;
-        st->status = ST_MAX_ITER;
-        st->iterations = st->max_iter + 1;
-        st->result = it & 1;
-        st->res_it = it;
-    }
-}
-
-static __global__ void k_rx_init(RxState* st, double rel_tol, double abs_tol, int max_iter,
-                                 int check_interval) {
-    if (threadIdx.x == 0) {
-        st->tol = 0.0;
-        st->abs_tol = abs_tol;
-        st->rel_tol = rel_tol;
-        st->res0 = st->res = 0.0;
-        st->iterations = 0;
-        st->done = 0;
-        st->status = ST_MAX_ITER;
-        st->max_iter = max_iter;
-        st->check_interval = check_interval;
-        st->result = 0;
-        st->res_it = 0;
-        st->res_exact = 1;
-        st->ovr_it = -1;
-        st->pad0 = 0;
-        st->ovr_m = 0.0;
-        st->bmax = 0.0;
-    }
-}
-
-// Boundary shell of an iteration: mode 0 copies src -> dst, mode 1 applies
-// the Neumann gathers to dst.
-static __global__ __launch_bounds__(256) void k_rx_shell(Geo g, const RxState* st,
-                                                  const double* __restrict__ src,
-                                                  double* __restrict__ dst, int mode) {
-    if (st->done) return;
-    const long long total = shell_total(g);
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-         e += (long long)gridDim.x * blockDim.x) {
-        int i, j, k;
-        bool zlo, zhi;
-        shell_cell(g, e, i, j, k, zlo, zhi);
-        const long long d = cidx(g, i, j, k);
-        if (mode == 0) {
-            dst[d] = src[d];
-        } else {
-            const int sk = (zlo || zhi) ? bc_map(k, g.nz, 0) : k;
-            dst[d] = dst[cidx(g, bc_map(i, g.nx, 0), bc_map(j, g.ny, 0), sk)];
-        }
-    }
-}
-
-// Z-slabs (DIST): the residual is an all-ranks max, through the device
-// mailbox (mb) or, without one, left encoded in dred[0] for an RCCL max
-// all-reduce + k_rx_finish.
-template <int TY, int MODE, int FL, bool DIST = false>
-static __global__ __launch_bounds__(64 * TY, sweep_min_waves<FL>()) void k_rx(
-    SGeo g, RelaxCoef rc, const double* __restrict__ xin, double* __restrict__ xout,
-    const double* __restrict__ rhs, RxState* st, double* partials, unsigned* counter, int it,
-    Mbox* mb, unsigned long long* dred) {
-    constexpr bool PF = (FL & SW_PREFETCH) != 0;
-    constexpr bool RES = MODE != RX_BLACK;
-    __shared__ double2 rows[2][TY + 2][64];
-    __shared__ double sh[TY];
-    __shared__ int flag;
-    if (st->done) return;
-    // stencil field: X (red / Jacobi) or Y in place (black)
-    const double* xs = (MODE == RX_BLACK) ? xout : xin;
-    RowPair c = row_pair<TY>(g);
-    const bool halo = (c.w == 0) || (c.w == TY - 1);
-    const int jh = (c.w == 0) ? max(c.j - 1, 0) : min(c.j + 1, g.ny - 1);
-    const int hslot = (c.w == 0) ? 0 : TY + 1;
-    const long long hoff = (long long)(jh - min(c.j, g.ny - 1)) * g.px;
-    const bool xok = c.i0 < g.nx;
-    const bool eok = (c.lane == 0 && c.i0 >= 1 && xok) || (c.lane == 63 && c.i0 + 2 < g.nx);
-    const long long eoff = (c.lane == 0) ? -1 : 2;
-    // parity (i+j+k) of the pair's first cell at local plane k is
-    // (j + k + kofs) & 1 (i0 even); the first colour pass updates odd cells
-    const int upd = (MODE == RX_RED) ? 1 : 0;
-    const double2 zero = make_double2(0.0, 0.0);
-    struct Bundle {
-        double2 pp, hp, rr;  // X centre / y-halo of plane k+1; rhs of plane k
-        double el;           // x-edge cell of plane k
-    };
-    auto issue = [&](int k, long long ix) __attribute__((always_inline)) {
-        const double2 zero = make_double2(0.0, 0.0);
-        Bundle b;
-        const long long ip = ix + g.sz;
-        b.pp = xok ? ld2(xs, ip) : zero;
-        b.hp = (xok && halo && k + 1 < c.ke) ? ld2(xs, ip + hoff) : zero;
-        b.rr = xok ? ld2v<FL>(rhs, ix) : zero;
-        b.el = eok ? xs[ix + eoff] : 0.0;
-        return b;
-    };
-    double m = 0.0;
-    long long idx = c.idx;
-    double2 pm = xok ? ld2(xs, idx - g.sz) : zero;
-    double2 pc = xok ? ld2(xs, idx) : zero;
-    double2 hc = (xok && halo) ? ld2(xs, idx + hoff) : zero;
-    Bundle cur;
-    if (PF) cur = issue(c.kb, idx);
-    int buf = 0;
-    for (int k = c.kb; k < c.ke; ++k, idx += g.ps) {
-        Bundle nxt;
-        if (PF) {
-            if (k + 1 < c.ke) nxt = issue(k + 1, idx + g.ps);
-        } else {
-            cur = issue(k, idx);
-        }
-        rows[buf][c.w + 1][c.lane] = pc;
-        if (halo) rows[buf][hslot][c.lane] = hc;
-        __syncthreads();
-        const double2 ys = rows[buf][c.w][c.lane];
-        const double2 yn = rows[buf][c.w + 2][c.lane];
-        const double2 pp = cur.pp;
-        double left = __shfl_up(pc.y, 1, 64);
-        double right = __shfl_down(pc.x, 1, 64);
-        if (c.lane == 0) left = cur.el;
-        if (c.lane == 63) right = cur.el;
-        // cell 0: (xm, xp) = (left, pc.y); cell 1: (pc.x, right)
-        if (RES) {  // linear_solver.c:304-346 (k_residual_linf's expression)
-            const double l0 = divc(pc.y - 2.0 * pc.x + left, rc.dx2, rc.rdx2) +
-                              divc(yn.x - 2.0 * pc.x + ys.x, rc.dy2, rc.rdy2) +
-                              (pp.x + pm.x - 2.0 * pc.x) * rc.inv_dz2;
-            const double l1 = divc(right - 2.0 * pc.y + pc.x, rc.dx2, rc.rdx2) +
-                              divc(yn.y - 2.0 * pc.y + ys.y, rc.dy2, rc.rdy2) +
-                              (pp.y + pm.y - 2.0 * pc.y) * rc.inv_dz2;
-            const double r0 = fabs(l0 - cur.rr.x), r1 = fabs(l1 - cur.rr.y);
-            if (c.in0 && r0 > m) m = r0;
-            if (c.in1 && r1 > m) m = r1;
-        }
-        double2 out = pc;
-        if (MODE == RX_JACOBI) {
-            const double pn0 = -(cur.rr.x - divc(pc.y + left, rc.dx2, rc.rdx2) -
-                                 divc(yn.x + ys.x, rc.dy2, rc.rdy2) -
-                                 (pp.x + pm.x) * rc.inv_dz2) *
-                               rc.inv_factor;
-            const double pn1 = -(cur.rr.y - divc(right + pc.x, rc.dx2, rc.rdx2) -
-                                 divc(yn.y + ys.y, rc.dy2, rc.rdy2) -
-                                 (pp.y + pm.y) * rc.inv_dz2) *
-                               rc.inv_factor;
-            if (c.in0) out.x = pn0;
-            if (c.in1) out.y = pn1;
-        } else {
-            // one cell of the pair has this pass's colour: gather its stencil
-            // (wave-uniform choice: the parity depends on j and k only)
-            const bool first = ((c.j + k + g.kofs) & 1) == upd;  // global parity
-            const double xc = first ? pc.x : pc.y;
-            const double xl = first ? left : pc.x, xr = first ? pc.y : right;
-            const double yl = first ? ys.x : ys.y, yr = first ? yn.x : yn.y;
-            const double zl = first ? pm.x : pm.y, zr = first ? pp.x : pp.y;
-            const double rh = first ? cur.rr.x : cur.rr.y;
-            const double pn = -(rh - divc(xr + xl, rc.dx2, rc.rdx2) -
-                                divc(yr + yl, rc.dy2, rc.rdy2) - (zr + zl) * rc.inv_dz2) *
-                              rc.inv_factor;
-            const double xn = xc + rc.omega * (pn - xc);
-            if (first) {
-                if (c.in0) out.x = xn;
-            } else if (c.in1) {
-                out.y = xn;
-            }
-        }
-        if (c.act) st2v<FL>(xout, idx, out);
-        pm = pc;
-        pc = pp;
-        hc = cur.hp;
-        if (PF) cur = nxt;
-        buf ^= 1;
-    }
-    if (!RES) return;
-    m = wave_max(m);
-    if (c.lane == 0) sh[c.w] = m;
-    __syncthreads();
-    double* shs = (double*)&rows[0][0][0];
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int q = 0; q < TY; ++q) a = fmax(a, sh[q]);
-        store_sc1(&partials[blockIdx.x], a);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned t = __hip_atomic_fetch_add((gu32*)counter, 1u, __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT);
-        flag = (t == gridDim.x - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (flag == 0) return;
-    double a = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += 64 * TY) a = fmax(a, load_sc1(&partials[b]));
-    a = wave_max(a);
-    if (c.lane == 0) shs[c.w] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int q = 0; q < TY; ++q) tot = fmax(tot, shs[q]);
-        __hip_atomic_store((gu32*)counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!DIST) {
-            rx_finish(st, tot, it);
-        } else if (mb) {
-            double gm;
-            if (mbox_allreduce(mb, tot, &gm, true)) {
-                rx_finish(st, gm, it);
-            } else {
-                st->done = 1;
-                st->status = ST_COMM_TIMEOUT;
-            }
-        } else {
-            dred[0] = ord_enc(tot);
-        }
-    }
-}
-
-__device__ __forceinline__ double ord_dec_dev(unsigned long long e) {
-    const unsigned long long b =
-        (e & 0x8000000000000000ull) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
-    return __longlong_as_double((long long)b);
-}
-
-// after the RCCL max all-reduce of dred (Z-slabs without a device mailbox)
-static __global__ void k_rx_finish(RxState* st, const unsigned long long* gred, int it) {
-    if (threadIdx.x == 0 && !st->done) rx_finish(st, ord_dec_dev(gred[0]), it);
-}
-
-// ---------------------------------------------------------------------------
-// Single-pass Red-Black SOR iteration (3-D, single device): X -> Y in one
-// z-march. For plane q the tile forms R_q = X_q with its first-colour ("red",
-// (i+j+k) odd) interior cells SOR-updated (linear_solver_redblack.c:97-114);
-// then the second colour of plane q-1 is updated from R (:116-133), and the
-// L-inf residual of X at plane q (linear_solver.c:304-346) rides along. R at
-// a tile's y/x halo is recomputed locally (overlapped tiles: 128 x 16 cells
-// loaded per plane, 124 x 12 written), so each cell of X and rhs is read
-// once from HBM and Y written once: 24 B/cell per iteration instead of the
-// two colour passes' 48. R values are computed from the same X values by the
-// same expression as the first pass would, so Y is bitwise the two-pass
-// result.
-// ---------------------------------------------------------------------------
-
-// One SOR update of a cell (linear_solver_redblack.c:103-112 operation order).
-template <class Dv>
-__device__ __forceinline__ double sor1(const RelaxCoef& rc, Dv dv, double vc, double vl, double vr,
-                                       double vs, double vn, double vm, double vp, double vb) {
-    const double pn = -(vb - dv(vr + vl, rc.dx2, rc.rdx2) - dv(vn + vs, rc.dy2, rc.rdy2) -
-                        (vp + vm) * rc.inv_dz2) *
-                      rc.inv_factor;
-    return vc + rc.omega * (pn - vc);
-}
-
-// |lap(x) - rhs| of one cell (linear_solver.c:304-346, the division form).
-template <class Dv>
-__device__ __forceinline__ double res1(const RelaxCoef& rc, Dv dv, double c, double xl, double xr,
-                                       double ys, double yn, double zm, double zp, double b) {
-    const double l = dv(xr - 2.0 * c + xl, rc.dx2, rc.rdx2) +
-                     dv(yn - 2.0 * c + ys, rc.dy2, rc.rdy2) + (zp + zm - 2.0 * c) * rc.inv_dz2;
-    return fabs(l - b);
-}
-
-template <bool V>
-using BoolC = std::integral_constant<bool, V>;
-template <int V>
-using IntC = std::integral_constant<int, V>;
-
-// Tile shapes (r02b). A workgroup is 16 waves; lane l of wave w owns the x
-// pair c = l % TC of tile row r = w + 16 (l / TC), so a tile is TC pairs (2 TC
-// columns) by TR = 1024 / TC rows. Rows w and w + 16 h have the same parity,
-// so the colour pattern of a step stays wave-uniform for every TC. R is
-// recomputed on the tile's one-cell halo: 2 TC - 4 columns and TR - 4 rows are
-// written per tile. TC = 64 (16 rows) loads 1.38x the cells it writes, TC = 32
-// (32 rows) 1.22x, and the narrower tiles also waste less on the last x tile
-// (512: 5 x 124 columns for 510 vs 9 x 60).
-template <int TC>
-constexpr int rb1_rows() { return 1024 / TC; }
-template <int TC>
-constexpr int rb1_ox() { return 2 * TC - 4; }  // output columns per tile
-template <int TC>
-constexpr int rb1_oy() { return 1024 / TC - 4; }  // output rows per tile
-
-// Issue-model details (r02; profiles/r02_rb_variants.jsonl, r02_pmc_rb.jsonl):
-//  - the colour pattern of a step is wave-uniform ((j + q) parity): the z
-//    loop is unrolled by two planes and each step is compiled for its
-//    pattern, so no per-lane selects pick the updated cell of a pair
-//    (VALU instructions per launch 321 M -> 196 M at 512^3);
-//  - x neighbours come from the row the wave already published in LDS (one
-//    ds_read_b64 each side) instead of two ds_bpermute per double, and every
-//    LDS operand of a step is read right after its barrier (one LDS round
-//    trip per step);
-//  - rhs is not loaded on the two halo rows, which never use it.
-// PF = the register-ring prefetch below (r02: 0.90 -> 0.76 ms per iteration at
-// 512^3 on one box, 128 VGPRs); the product instantiates PF = true.
-// DIST (Z-slabs): R on a halo plane that has a neighbour (rh_lo: plane k0 - 1,
-// rh_hi: plane k1) is the neighbour's R of its edge plane, exchanged into RH
-// beforehand (k_rb_edge_r + halo); it cannot be formed here, since that needs
-// X two planes beyond the halo. The L-inf residual leaves as in k_rx: the
-// device mailbox's max, or dred for an RCCL max all-reduce + k_rx_finish.
-// LDS of one k_rb1 workgroup: X and R rows of two plane parities (the same
-// 64 KB for every tile width), the waves' residual maxima and the
-// last-workgroup flag.
-struct Rb1Lds {
-    double xb[2 * 1024 * 2];
-    double rb[2 * 1024 * 2];
-    double sh[16];
-    int flag;
-};
-
-// The body of k_rb1 for the tile width TC; bid = this workgroup's tile-block
-// index within its geometry g (k_rb1m runs two geometries in one grid).
-template <int FL, int TC, bool PF, bool DIST, bool REV = false>
-__device__ __forceinline__ void rb1_body(
-    Rb1Lds& L, int bid, SGeo g, RelaxCoef rc, const double* __restrict__ X,
-    double* __restrict__ Y, const double* __restrict__ rhs, RxState* st, double* partials,
-    unsigned* counter, int it, const double* __restrict__ RH, int rh_lo, int rh_hi, Mbox* mb,
-    unsigned long long* dred, int neu) {
-    constexpr int NW = 16;  // waves
-    constexpr int TR = rb1_rows<TC>();
-    constexpr int OX = rb1_ox<TC>(), OY = rb1_oy<TC>();
-    // X and R rows by plane parity; a row is stored as its TC .x cells, then
-    // its TC .y cells, so a pair is one ds_read2/ds_write2_b64 and an x
-    // neighbour (one double of the adjacent lane) a conflict-free ds_read_b64
-    // (with double2 rows those 8-B reads at a 16-B lane stride conflicted)
-    auto& xb = *reinterpret_cast<double(*)[2][TR][2][TC]>(L.xb);
-    auto& rb = *reinterpret_cast<double(*)[2][TR][2][TC]>(L.rb);
-    auto& sh = L.sh;
-    auto& flag = L.flag;
-    // every LDS read stays a ds_read_b64 (2 LDS cycles per wave; a pair
-    // merged into ds_read2_b64 takes 8): a scheduling barrier that lets every
-    // instruction class cross it ends the pairing pass's search window
-    auto lrd = [&](const double& v) __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0x7ff);
-        return v;
-    };
-    auto lget = [&](double (&a)[2][TR][2][TC], int p, int r, int l) __attribute__((always_inline)) {
-        const double x = lrd(a[p][r][0][l]);
-        return make_double2(x, lrd(a[p][r][1][l]));
-    };
-    auto lput = [&](double (&a)[2][TR][2][TC], int p, int r, int l, double2 v)
-                    __attribute__((always_inline)) {
-        a[p][r][0][l] = v.x;
-        a[p][r][1][l] = v.y;
-    };
-    if (st->done) return;
-    // tile = block index: round-robin dispatch spreads consecutive tiles over
-    // the eight XCDs (r03: faster here than xcd_tile's contiguous ranges,
-    // 2.86-2.87 -> 2.82-2.83 ms per iteration at 1024^2 x 512, equal at 512^3,
-    // profiles/r03_tile_order.jsonl)
-    const int t = bid;
-    const int tx = t % g.tiles_x;
-    const int rest = t / g.tiles_x;
-    const int ty = rest % g.tiles_y;
-    const int tz = rest / g.tiles_y;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int c = lane % TC;                     // pair within the row
-    const int r = w + NW * (lane / TC);          // tile row
-    const int cm = max(c - 1, 0), cp = min(c + 1, TC - 1);  // x neighbours' pairs
-    const int rlo = max(r - 1, 0), rhi = min(r + 1, TR - 1);  // y neighbours' rows
-    const int i0 = g.xofs + tx * OX - 2 + 2 * c;  // even; the pair is (i0, i0 + 1)
-    const int j = ty * OY - 2 + r;       // grid row
-    // kmode 1: the slab's two edge planes (tz 0 -> k0, tz 1 -> k1 - 1);
-    // kmode 2: the planes [kt0, kt1); else [k0, k1). A march over a plane
-    // range still forms R on its two lower neighbour planes (prologue), so
-    // the ranges of one iteration's launches give the one-launch Y.
-    int kb, ke;
-    if (g.kmode == 1) {
-        kb = (tz == 0) ? g.k0 : g.k1 - 1;
-        ke = kb + 1;
-    } else {
-        const int kt0 = (g.kmode == 2) ? g.kt0 : g.k0;
-        const int kt1 = (g.kmode == 2) ? g.kt1 : g.k1;
-        kb = kt0 + tz * g.kc;
-        ke = min(kb + g.kc, kt1);
-    }
-    const bool xin = (i0 >= 0 && i0 < g.nx);
-    const bool ld = xin && j >= 0 && j < g.ny;
-    const bool jin = (j >= 1 && j <= g.ny - 2);
-    const bool in0 = jin && i0 >= 1 && i0 <= g.nx - 2;
-    const bool in1 = jin && i0 + 1 <= g.nx - 2;
-    const bool orow = (r >= 2 && r < 2 + OY);
-    const bool own = orow && c >= 1 && c <= TC - 2;
-    // wave-uniform skips: with TC = 64 a wave is one row, so its halo rows
-    // (no R work: rows 0, 15; no output: rows 0, 1, 14, 15) skip whole
-    // phases; narrower tiles mix rows in a wave and mask per lane instead
-    const bool wr = (TC == 64) ? (r >= 1 && r <= TR - 2) : true;
-    const bool wo = (TC == 64) ? orow : true;
-    const long long col = (long long)max(min(j, g.ny - 1), 0) * g.px + max(i0, 0);
-    // the folded Neumann shell (neu): this lane's x-face roles and whether it
-    // stores (pairs (nx-1, pad) of odd nx leave cell nx-1 to role 4)
-    const int nrole = (i0 == 0 ? 1 : 0) | (i0 + 1 == g.nx - 1 ? 2 : 0) |
-                      (i0 + 1 == g.nx - 2 ? 4 : 0) |
-                      ((own && jin && i0 <= g.nx - 2) ? 8 : 0);
-    // Loads are issued unconditionally from clamped (always valid) addresses
-    // and never masked: with the same loads on every control path and no
-    // select right behind them, the compiler's vmcnt counting waits for a
-    // plane only where a step consumes it (a load some path skips, or a
-    // select on the loaded value, forces vmcnt(0) right after the prefetch of
-    // the next plane, i.e. a full memory latency per step). Positions outside
-    // the grid (ld false, k out of range) then hold other cells' values; they
-    // only ever feed boundary cells, which are not updated, and halo lanes,
-    // which are not stored or reduced. The halo rows 0 and TR - 1 (no R work)
-    // load the adjacent row's rhs, which that row's lanes load too (an L2 hit).
-    const int ic = (i0 < g.nx) ? max(i0, 0) : g.nx - 2 - ((g.nx - 2) & 1);
-    const int jr = j + (r == 0 ? 1 : (r == TR - 1 ? -1 : 0));
-    const long long colx = (long long)max(min(j, g.ny - 1), 0) * g.px + ic;
-    const long long colr = (long long)max(min(jr, g.ny - 1), 0) * g.px + ic;
-    auto ldx = [&](int k) -> double2 {
-        return ld2(X, (long long)min(max(k, 0), g.nz - 1) * g.ps + colx);
-    };
-    auto ldr = [&](int k) -> double2 {
-        return ld2v<FL>(rhs, (long long)min(max(k, 0), g.nz - 1) * g.ps + colr);
-    };
-    const double2 zero = make_double2(0.0, 0.0);
-    // Step q forms R_{q+1} and updates the second colour of plane q.
-    // Per lane: X_q, X_{q+1}, X_{q+2} (xm, xc, xp); R_{q-1}, R_q (rmm, rm);
-    // rhs_{q+1} (bq). Of rhs_q and R_{q-1} only the component of the cell
-    // this step's second-colour update touches is kept (bmh, rmmh): the
-    // pattern alternates per plane, so the end of step q keeps the component
-    // step q + 1 will use. LDS at the top of step q: X_{q+1} rows in
-    // xb[(q+1)&1], R_q rows in rb[q&1].
-    // PF (register ring): the X planes sit in a ring of four register slots
-    // and rhs in a ring of two, indexed by the step's phase P = (q - q0) mod 4
-    // at compile time (the z loop is unrolled by four), and step q issues the
-    // loads of X_{q+3} and rhs_{q+2} into the free slots before its barrier:
-    // a full step of latency hiding, and no register copy of a loaded value
-    // (a copy would wait for the load). Without PF the loads are issued at
-    // the end of step q and the three X planes shift through xm, xc, xp.
-    // REV (r03, one device): the march runs z downwards, D = -1: step q forms
-    // R_{q-1} and updates plane q, "ahead" is q - 1. Every cell's operands
-    // keep their z roles (z- / z+ are picked by direction), R depends on X
-    // only and the second colour on R only, and the residual is a max, so Y
-    // and the iteration's decision are bitwise the upward march's. The host
-    // alternates the direction per iteration, so each sweep starts on the
-    // planes the previous one wrote last (in the Infinity Cache).
-    constexpr int D = REV ? -1 : 1;
-    const int q0 = REV ? ke + 1 : kb - 2;  // the first step
-    double2 xr[4], br[2], rm;
-    double bmh, rmmh;
-    xr[0] = ldx(q0);
-    xr[1] = ldx(q0 + D);
-    xr[2] = ldx(q0 + 2 * D);
-    xr[3] = zero;
-    br[0] = ldr(q0 + D);
-    br[1] = zero;
-    rm = zero;
-    bmh = rmmh = 0.0;
-    lput(xb, (q0 + D) & 1, r, c, xr[1]);
-    double m = 0.0;
-    // E: cell i0 of the pair is the cell both updates of this step touch (the
-    // first colour, (i+j+k) odd, of plane q+1 and the second of plane q)
-    auto step = [&](auto Ec, auto Pc, int q) __attribute__((always_inline)) {
-        constexpr bool E = decltype(Ec)::value;
-        constexpr int P = PF ? decltype(Pc)::value : 0;  // ring phase
-        constexpr int IM = P & 3, IC = (P + 1) & 3, IP = (P + 2) & 3, IN = (P + 3) & 3;
-        constexpr int BQ = P & 1, BN = (P + 1) & 1;
-        if constexpr (PF) {
-            xr[IN] = ldx(q + 3 * D);
-            br[BN] = ldr(q + 2 * D);
-        }
-        // behind / centre / ahead of plane qa, then its z- / z+ neighbours
-        const double2 xbh = xr[IM], xc = xr[IC], xah = xr[IP], bq = br[BQ];
-        const double2 xm = REV ? xah : xbh, xp = REV ? xbh : xah;
-        __syncthreads();
-        const int qa = q + D;
-        const bool qin = (qa >= g.k0 && qa < g.k1);
-        const bool rin = qin && qa >= kb && qa < ke;
-        // the output's LDS operands (R_q rows) are read up front, so one LDS
-        // round trip after the barrier serves both halves of the step
-        const double2 rys = lget(rb, q & 1, rlo, c);
-        const double2 ryn = lget(rb, q & 1, rhi, c);
-        const double rlr = lrd(E ? rb[q & 1][r][1][cm] : rb[q & 1][r][0][cp]);
-        double2 R = xc;
-        if constexpr (DIST) {
-            if ((qa == g.k0 - 1 && rh_lo) || (qa == g.k1 && rh_hi))
-                R = ld2(RH, (long long)qa * g.ps + colx);
-        }
-        const double2 ys = lget(xb, qa & 1, rlo, c);
-        const double2 yn = lget(xb, qa & 1, rhi, c);
-        const double left = lrd(xb[qa & 1][r][1][cm]);
-        const double right = lrd(xb[qa & 1][r][0][cp]);
-        if (wr && qin) {
-            if (E) {
-                const double v = sor1(rc, DivC{}, xc.x, left, xc.y, ys.x, yn.x, xm.x, xp.x, bq.x);
-                if (in0) R.x = v;
-            } else {
-                const double v = sor1(rc, DivC{}, xc.y, xc.x, right, ys.y, yn.y, xm.y, xp.y, bq.y);
-                if (in1) R.y = v;
-            }
-            if (wo && rin) {
-                const double a0 = res1(rc, DivC{}, xc.x, left, xc.y, ys.x, yn.x, xm.x, xp.x, bq.x);
-                const double a1 = res1(rc, DivC{}, xc.y, xc.x, right, ys.y, yn.y, xm.y, xp.y, bq.y);
-                if (own && in0 && a0 > m) m = a0;
-                if (own && in1 && a1 > m) m = a1;
-            }
-        }
-        // ---- second colour of plane q from R_{q-1}, R_q, R_{q+1} ----
-        // (rmmh: R behind, R: R ahead; REV swaps their z roles)
-        if ((REV ? q < ke : q >= kb) && wo) {
-            double2 out = rm;
-            if (E) {
-                const double rzm = REV ? R.x : rmmh, rzp = REV ? rmmh : R.x;
-                const double v = sor1(rc, DivC{}, rm.x, rlr, rm.y, rys.x, ryn.x, rzm, rzp, bmh);
-                if (own && in0) out.x = v;
-            } else {
-                const double rzm = REV ? R.y : rmmh, rzp = REV ? rmmh : R.y;
-                const double v = sor1(rc, DivC{}, rm.y, rm.x, rlr, rys.y, ryn.y, rzm, rzp, bmh);
-                if (own && in1) out.y = v;
-            }
-            if (neu) {
-                // the iteration's Neumann BC (linear_solver_redblack.c:139) folded
-                // into the stores: every boundary cell of Y is the gather
-                // k_bc_shell / k_rx_shell mode 1 makes, Y at the clamped-inward
-                // position (bc_map), so the writer of that source cell stores
-                // it to its mirror positions too: x faces within the pair (or
-                // one 8-B store when nx is odd), y faces as a copy of rows 1 /
-                // ny-2, z faces (global, not a slab's halo) as copies of
-                // planes k0 / k1-1
-                // nrole (lane constant): 1 = pair (0, 1), 2 = pair (nx-2, nx-1),
-                // 4 = nx odd and .y is cell nx-2 (cell nx-1 <- .y), 8 = store
-                if (nrole & 1) out.x = out.y;
-                if (nrole & 2) out.y = out.x;
-                if (nrole & 8) {
-                    // j is wave-uniform with TC = 64 (one row per wave), so
-                    // are q and the z-face tests: scalar branches
-                    auto put = [&](long long base) __attribute__((always_inline)) {
-                        st2v<FL>(Y, base, out);
-                        if (nrole & 4) Y[base + 2] = out.y;
-                        if (j == 1 || j == g.ny - 2) {
-                            const long long b2 = base + (j == 1 ? -g.px : g.px);
-                            st2v<FL>(Y, b2, out);
-                            if (nrole & 4) Y[b2 + 2] = out.y;
-                        }
-                    };
-                    const long long base = (long long)q * g.ps + col;
-                    put(base);
-                    if (q == g.k0 && !rh_lo) put(base - g.ps);
-                    if (q == g.k1 - 1 && !rh_hi) put(base + g.ps);
-                }
-            } else if (own && ld && jin) {
-                st2v<FL>(Y, (long long)q * g.ps + col, out);
-            }
-        }
-        // step q + D updates the .x cell iff this step did not
-        rmmh = E ? rm.y : rm.x;
-        rm = R;
-        bmh = E ? bq.y : bq.x;
-        if constexpr (!PF) {
-            xr[0] = xc;
-            xr[1] = xah;
-            xr[2] = ldx(q + 3 * D);
-            br[0] = ldr(q + 2 * D);
-        }
-        // publish X_{q+2} and R_{q+1} for step q + 1 (their buffers were last
-        // read in step q - 1, before this step's barrier)
-        lput(xb, (q + 2 * D) & 1, r, c, xah);
-        lput(rb, (q + D) & 1, r, c, rm);
-    };
-    // E(q) for the lane's row: ((j + q + kofs) & 1) == 0; E(kb - 2) == E(kb);
-    // rows r and r + 16 h share the parity, so E is wave-uniform
-    const bool E0 = __builtin_amdgcn_readfirstlane(((j + q0 + g.kofs) & 1) == 0 ? 1 : 0) != 0;
-    // steps q0, q0 + D, ...: ke - kb + 2 of them (R is formed one plane ahead)
-    const int nsteps = ke - kb + 2;
-    int n = 0;
-    auto march = [&](auto E0c) __attribute__((always_inline)) {
-        constexpr bool A = decltype(E0c)::value;
-        using TA = BoolC<A>;
-        using TB = BoolC<!A>;
-        if constexpr (PF) {
-            for (; n + 3 < nsteps; n += 4) {
-                step(TA{}, IntC<0>{}, q0 + D * n);
-                step(TB{}, IntC<1>{}, q0 + D * (n + 1));
-                step(TA{}, IntC<2>{}, q0 + D * (n + 2));
-                step(TB{}, IntC<3>{}, q0 + D * (n + 3));
-            }
-            if (n < nsteps) step(TA{}, IntC<0>{}, q0 + D * n);
-            if (n + 1 < nsteps) step(TB{}, IntC<1>{}, q0 + D * (n + 1));
-            if (n + 2 < nsteps) step(TA{}, IntC<2>{}, q0 + D * (n + 2));
-        } else {
-            for (; n + 1 < nsteps; n += 2) {
-                step(TA{}, IntC<0>{}, q0 + D * n);
-                step(TB{}, IntC<0>{}, q0 + D * (n + 1));
-            }
-            if (n < nsteps) step(TA{}, IntC<0>{}, q0 + D * n);
-        }
-    };
-    if (E0) march(BoolC<true>{});
-    else march(BoolC<false>{});
-    m = wave_max(m);
-    if (lane == 0) sh[w] = m;
-    __syncthreads();
-    double* shs = &xb[0][0][0][0];
-    // an iteration split over several launches (slabs: kmode 1 / 2) shares
-    // one partials array: this launch owns [part_ofs, part_ofs + gridDim.x)
-    // of part_total, and the last of all part_total workgroups (the last
-    // launch on the stream) finishes the max
-    const unsigned ptot = g.part_total ? (unsigned)g.part_total : gridDim.x;
-    if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int v = 0; v < NW; ++v) a = fmax(a, sh[v]);
-        store_sc1(&partials[g.part_ofs + blockIdx.x], a);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned tk = __hip_atomic_fetch_add((gu32*)counter, 1u, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        flag = (tk == ptot - 1) ? 1 : 0;
-    }
-    __syncthreads();
-    if (flag == 0) return;
-    double a = 0.0;
-    for (unsigned b = threadIdx.x; b < ptot; b += 1024) a = fmax(a, load_sc1(&partials[b]));
-    a = wave_max(a);
-    if (lane == 0) shs[w] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (int v = 0; v < NW; ++v) tot = fmax(tot, shs[v]);
-        __hip_atomic_store((gu32*)counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!DIST) {
-            rx_finish(st, tot, it);
-        } else if (mb) {
-            double gm;
-            if (mbox_allreduce(mb, tot, &gm, true)) {
-                rx_finish(st, gm, it);
-            } else {
-                st->done = 1;
-                st->status = ST_COMM_TIMEOUT;
-            }
-        } else {
-            dred[0] = ord_enc(tot);
-        }
-    }
-}
-
-template <int FL, int TC, bool PF, bool DIST = false, bool REV = false>
-static __global__ __launch_bounds__(1024, 4) void k_rb1(
-    SGeo g, RelaxCoef rc, const double* __restrict__ X, double* __restrict__ Y,
-    const double* __restrict__ rhs, RxState* st, double* partials, unsigned* counter, int it,
-    const double* __restrict__ RH, int rh_lo, int rh_hi, Mbox* mb, unsigned long long* dred,
-    int neu) {
-    __shared__ Rb1Lds L;
-    rb1_body<FL, TC, PF, DIST, REV>(L, blockIdx.x, g, rc, X, Y, rhs, st, partials, counter, it, RH,
-                               rh_lo, rh_hi, mb, dred, neu);
-}
-
-// One device, one launch: the full-width (TC 64) tiles of g64 in blocks
-// [0, nb64) and the narrow strip of the columns past them (g2, tile width
-// TC2) in the rest. A row's last TC-64 tile would be partial unless 124
-// divides it, and costs a full tile's steps for its few columns (512^3: 14
-// of 124); the strip's TC-16 / TC-32 tiles are 60 / 28 rows tall, so the
-// column strip needs 4.8x / 2.2x fewer workgroups. Both geometries share the
-// grid-wide residual reduction (part_total 0: gridDim.x workgroups).
-template <int FL, int TC2, bool REV = false>
-static __global__ __launch_bounds__(1024, 4) void k_rb1m(
-    SGeo g64, SGeo g2, int nb64, RelaxCoef rc, const double* __restrict__ X,
-    double* __restrict__ Y, const double* __restrict__ rhs, RxState* st, double* partials,
-    unsigned* counter, int it, int neu) {
-    __shared__ Rb1Lds L;
-    if ((int)blockIdx.x < nb64)
-        rb1_body<FL, 64, true, false, REV>(L, blockIdx.x, g64, rc, X, Y, rhs, st, partials,
-                                           counter, it, nullptr, 0, 0, nullptr, nullptr, neu);
-    else
-        rb1_body<FL, TC2, true, false, REV>(L, blockIdx.x - nb64, g2, rc, X, Y, rhs, st,
-                                            partials, counter, it, nullptr, 0, 0, nullptr,
-                                            nullptr, neu);
-}
-
-// R (the first colour SOR-updated, linear_solver_redblack.c:97-114) of a
-// slab's two edge planes k0 and k1 - 1 into RH, for the neighbours' k_rb1
-// (DIST); same operands and order as k_rb1's R, so bitwise equal to it.
-static __global__ __launch_bounds__(256) void k_rb_edge_r(SGeo g, RelaxCoef rc,
-                                                         const double* __restrict__ X,
-                                                         const double* __restrict__ rhs,
-                                                         double* __restrict__ RH) {
-    const long long plane = (long long)g.nx * g.ny;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < 2 * plane;
-         e += (long long)gridDim.x * blockDim.x) {
-        const int k = (e < plane) ? g.k0 : g.k1 - 1;
-        const long long q = e % plane;
-        const int j = (int)(q / g.nx), i = (int)(q % g.nx);
-        if (i < 1 || i > g.nx - 2 || j < 1 || j > g.ny - 2) continue;
-        const long long c = (long long)k * g.ps + (long long)j * g.px + i;
-        double v = X[c];
-        if (((i + j + k + g.kofs) & 1) == 1)
-            v = sor1(rc, DivC{}, X[c], X[c - 1], X[c + 1], X[c - g.px], X[c + g.px], X[c - g.ps],
-                     X[c + g.ps], rhs[c]);
-        RH[c] = v;
-    }
-}
-
-
 // ===========================================================================
 // Predictor (solver_projection.c:116-185, with compute_source_terms
 // solver_explicit_euler.c:317-333 at iter = 0 as per-row / per-column tables
@@ -2851,26 +1168,6 @@ static __global__ __launch_bounds__(256) void k_rb_edge_r(SGeo g, RelaxCoef rc,
 #define CFD_PR_SYNC 1
 #endif
 // PR_TY rows (waves) per workgroup (tile_plan.hpp, -DCFD_PR_TY)
-
-// a / d correctly rounded, like divc, for operands that are often exactly
-// zero (derivatives of a field at rest): e = q d - a and q - e r give the
-// signed zero of a / d for a = +-0, so zeros stay on the fast path.
-__device__ __forceinline__ double divz(double a, double d, double r) {
-    const double q = a * r;
-    const double aq = fabs(q);
-    if (!(aq <= 0x1p+900 && (aq >= 0x1p-900 || aq == 0.0))) return a / d;
-    return fma(-fma(q, d, -a), r, q);
-}
-// divz with the range test deferred into a lane flag (see DivC)
-struct DivFastZ {
-    bool& ok;
-    __device__ __forceinline__ double operator()(double a, double d, double r) const {
-        const double q = a * r;
-        const double aq = fabs(q);
-        ok &= (aq <= 0x1p+900) & ((aq >= 0x1p-900) | (aq == 0.0));
-        return fma(-fma(q, d, -a), r, q);
-    }
-};
 
 struct ZTile {
     int i0, j, kb, ke, lane;

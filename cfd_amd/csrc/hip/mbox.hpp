@@ -1,5 +1,6 @@
 // mbox.hpp -- descriptor of the device mailbox used by the one-shot Z-slab
-// all-reduce (kernels.hpp mbox_allreduce; set up in slab_comm.hip).
+// all-reduce (mbox_allreduce below, called by the CG and relaxation sweeps;
+// set up in slab_comm.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

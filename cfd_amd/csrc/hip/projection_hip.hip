@@ -15,6 +15,19 @@
 #include <array>
 #include "poisson_solve.hpp"
 
+static __global__ void k_init_red(unsigned long long* red) {
+    if (threadIdx.x == 0) {
+        red[0] = 0x8000000000000000ull;  // enc(+0.0): reference maxima start at 0.0
+        red[1] = 0x8000000000000000ull;
+        red[2] = 0ull;
+        red[5] = 0ull;
+        red[3] = 0x000FFFFFFFFFFFFFull;  // enc(-inf)
+        red[4] = 0x8000000000000000ull;
+    }
+}
+
+void launch_init_red(hip_proj_ctx* c) { klaunch(c, k_init_red, dim3(1), dim3(64), c->red); }
+
 cfd_status_t ctx_validate_params(const hip_proj_ctx* c, const grid* g,
                                     const ns_solver_params_t* prm) {
     if (!g || !prm) return CFD_ERROR_INVALID;
@@ -67,6 +80,20 @@ cfd_status_t ctx_validate_params(const hip_proj_ctx* c, const grid* g,
                     "projection_hip: Z-slabs need periodic thermal BCs on both z faces or neither");
             return CFD_ERROR_UNSUPPORTED;
         }
+    }
+    return CFD_SUCCESS;
+}
+
+// The two fields init_ctx (below) leaves to their first user: rhs and x_tmp.
+cfd_status_t ensure_aux(hip_proj_ctx* c, bool need_rhs, bool need_xt) {
+    const size_t n = field_elems(c);
+    if (need_rhs && !c->rhs) {
+        cfd_status_t s = dalloc(c, &c->rhs, n);
+        if (s != CFD_SUCCESS) return s;
+    }
+    if (need_xt && !c->xt) {
+        cfd_status_t s = dalloc(c, &c->xt, n);
+        if (s != CFD_SUCCESS) return s;
     }
     return CFD_SUCCESS;
 }
@@ -403,9 +430,7 @@ static hip_proj_ctx* create_common(size_t nx, size_t ny, size_t nz_local, size_t
         // up lazily on a rank thread (the aux fields, the loop state, the
         // library's code object, which a kernel attribute query loads) is set
         // up here, at creation
-        hipFuncAttributes fa;
-        bool ok = hipFuncGetAttributes(&fa, (const void*)k_rx_init) == hipSuccess &&
-                  ensure_aux(c, true, true) == CFD_SUCCESS;
+        bool ok = relax_preload() && ensure_aux(c, true, true) == CFD_SUCCESS;
         if (ok && !c->rxst) ok = hipMalloc((void**)&c->rxst, sizeof(RxState)) == hipSuccess;
         if (ok && !c->rxst2) ok = hipMalloc((void**)&c->rxst2, sizeof(RxState)) == hipSuccess;
         if (!ok) {
@@ -591,7 +616,7 @@ cfd_status_t hip_proj_apply_scalar_bc(hip_proj_ctx_t* c, int id, bc_type_t type)
         // z copy (plane 0 <- nz-2, nz-1 <- 1) as a wrap-around halo exchange
         Geo g = c->geo;
         g.lo_face = g.hi_face = 0;
-        klaunch(c, k_bc_shell, dim3(shell_blocks(c)), dim3(256), g, d, mode, DirVals{});
+        launch_bc_geo(c, g, d, mode, DirVals{});
         HIP_TRY(hipGetLastError());
         return halo(c, {d}, true);
     }
@@ -894,7 +919,7 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
     cc.r_two_dx = pc.r_two_dx;
     cc.r_two_dy = pc.r_two_dy;
     cc.dt_over_rho = dt / rho;
-    klaunch(c, k_init_red, dim3(1), dim3(64), c->red);
+    launch_init_red(c);
     timed(c, HIP_KT_CORRECTOR, [&] {
         auto c3 = [&](auto kern) {
             klaunch(c, kern, dim3(np3), dim3(64 * PC_TY), c->pgeo16, cc, c->us, c->vs, c->ws, c->pn,

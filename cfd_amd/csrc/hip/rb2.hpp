@@ -60,7 +60,7 @@
 // range test, res1) and decides exactly: the bitwise baseline of the APX form.
 #pragma once
 
-#include "kernels.hpp"
+#include "relax_kernels.hpp"
 
 namespace cfdhip {
 

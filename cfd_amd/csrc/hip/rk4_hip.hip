@@ -13,6 +13,7 @@
 // between the context's CG work arrays (u*,v*,w*,p_new and r,p_a,p_b,x_tmp);
 // the final update is written in place over u,v,w,p.
 #include "ctx.hpp"
+#include "rk_kernels.hpp"
 #include "../host/grid_spacing.h"
 
 // stages: the running k sums and x_tmp (RK4 / RK2); explicit Euler needs neither
@@ -153,7 +154,7 @@ static cfd_status_t step_tail(hip_proj_ctx* c, const grid* g, const ns_solver_pa
                               ns_solver_stats_t* stats, bool velocity_bcs, const char* nan_msg) {
     const bool energy = (prm->alpha > 0.0);
     const size_t nz = c->nzg;
-    hipLaunchKernelGGL(k_init_red, dim3(1), dim3(64), 0, c->stream, c->red);
+    launch_init_red(c);
     if (energy) ST_TRY(ctx_energy_step(c, g, prm, false));
     // apply_boundary_conditions: periodic copies of every field (x, y, z faces)
     if (velocity_bcs)

@@ -36,7 +36,7 @@ struct SlabComm {
     virtual cfd_status_t allreduce_max_u64(hipStream_t s, const unsigned long long* in,
                                            unsigned long long* out, int n) = 0;
     // Device mailbox for the one-shot CG dot all-reduce fused into the sweeps
-    // (kernels.hpp mbox_allreduce); nullptr = all-reduce through allreduce_sum.
+    // (mbox.hpp mbox_allreduce); nullptr = all-reduce through allreduce_sum.
     virtual cfdhip::Mbox* device_mailbox() { return nullptr; }
     // the in-process group whose host lock this rank's calls take (ctx.hpp
     // GroupHostLock); nullptr for RCCL

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- inputs that drive the fast-division fallbacks
-(kernels.hpp divc / divz / DivFastZ + DivExact, rb2.hpp) and the bitwise
+(device_util.hpp divc / divz / DivFastZ + DivExact, rb2.hpp) and the bitwise
 comparison that sees signed zeros and NaNs (test_special_values.py proves on
 the oracle alone that the inputs reach both sides of the thresholds;
 test_gpu_special_values.py runs the kernels on them).

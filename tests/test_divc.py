@@ -1,5 +1,5 @@
 """The correctly rounded constant-divisor division of the relaxation sweeps
-(kernels.hpp `divc`): tools/divc_check.c restates it on the host and compares
+(device_util.hpp `divc`): tools/divc_check.c restates it on the host and compares
 it bit for bit with `/` over random quotients for the grid spacings the tests
 and BASELINE configs use (the full 9.6e8-quotient run is recorded in
 DESIGN.md; here 1e6 per divisor)."""

@@ -1,4 +1,4 @@
-/* CPU check of the divc() correction in cfd_amd/csrc/hip/kernels.hpp:
+/* CPU check of the divc() correction in cfd_amd/csrc/hip/device_util.hpp:
  * q = RN(a * RN(1/d)), q' = RN(q + RN(a - q d) * RN(1/d)) (two FMAs) against
  * the correctly rounded a / d, bit for bit, for the divisors dx^2 of grids of
  * n = 17 .. 1025 points on domains of length 1, 2*pi and 0.5, over random a
