@@ -40,6 +40,7 @@ HIP_POISSON_REDBLACK = 1
 HIP_POISSON_JACOBI = 2
 HIP_POISSON_BICGSTAB = 3  # hip_proj_poisson_solve / _ex only, not a projection-step method
 HIP_POISSON_DST = 4  # direct sine-transform solve: poisson_solve / _ex and the projection step
+HIP_POISSON_DCT = 5  # direct cosine-transform solve of the Neumann problem (BC_NEUMANN only)
 HIP_FIELD_U, HIP_FIELD_V, HIP_FIELD_W, HIP_FIELD_P, HIP_FIELD_T, HIP_FIELD_RHO = range(6)
 KERNEL_TIMERS = ["predictor", "cg_setup", "cg_sweep_a", "cg_sweep_b", "corrector",
                  "relax", "residual", "energy", "rk_stage", "cg_sweep_bx", "cc_update",

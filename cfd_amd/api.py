@@ -790,6 +790,15 @@ class HipProjection:
         return self._lib().hip_proj_dst_transform(self._ctx, field.ctypes.data_as(A.c_double_p),
                                                   axis)
 
+    def dct_transform(self, field: np.ndarray, axis: int, inverse: bool = False) -> int:
+        """hip_proj_dct_transform: the orthonormal type-II cosine transform of
+        the interior of `field` along axis 0 (x), 1 (y) or 2 (z), in place, or
+        its inverse (one transform pass of HIP_POISSON_DCT); returns the status."""
+        assert field.dtype == np.float64 and field.flags["C_CONTIGUOUS"]
+        assert field.shape == self.shape, (field.shape, self.shape)
+        return self._lib().hip_proj_dct_transform(self._ctx, field.ctypes.data_as(A.c_double_p),
+                                                  axis, 1 if inverse else 0)
+
     def cg_fixed_iters(self, rhs: np.ndarray, dx, dy, dz, iters: int) -> float:
         a = np.ascontiguousarray(rhs, dtype=np.float64)
         return self._lib().hip_proj_cg_fixed_iters(self._ctx, a.ctypes.data_as(A.c_double_p),

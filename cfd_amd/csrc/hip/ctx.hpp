@@ -38,6 +38,16 @@ struct DstTable {
     double* e;
 };
 
+// ... of the cosine-transform solver (dct_solve.hpp): Q_n for the inverse
+// pass, its transpose for the forward pass (the passes apply the transpose of
+// the table they are given), and the Neumann e_n
+struct DctTable {
+    int n, np;
+    double* Q;
+    double* Qt;
+    double* e;
+};
+
 // Error reporting goes through the host library's thread-local error state
 // (cfd_set_error, logging.c:39-46 in the reference). Weak, so the library
 // links against either the reference's host library or ours.
@@ -149,6 +159,9 @@ struct hip_proj_ctx : TilePlan {
     // axis length by the first such solve, and the events around a solve
     std::vector<DstTable> dst_tabs;
     hipEvent_t dst_ev[2] = {nullptr, nullptr};
+    // cosine-transform solver (dct_solve.hpp): its tables, cached the same
+    // way; it shares the events
+    std::vector<DctTable> dct_tabs;
     // monitoring (derived_stats.hip), allocated by the first such call: the
     // statistics pass's workgroup records, totals and ticket; the velocity
     // magnitude in the padded layout
@@ -450,6 +463,10 @@ cfd_status_t relax_solve(hip_proj_ctx* c, int method, double dx, double dy, doub
                          double rel_tol, double abs_tol, int max_iter, int check_interval,
                          double omega_in) __attribute__((visibility("hidden")));
 bool relax_preload() __attribute__((visibility("hidden")));
+// The relaxation solvers' L-infinity residual of x against ctx->rhs
+// (k_residual_linf, as relax_solve forms it), for the direct cosine solve.
+cfd_status_t relax_residual_linf(hip_proj_ctx* c, const double* x, double dx, double dy,
+                                 double dz, double* out) __attribute__((visibility("hidden")));
 // The lazily allocated rhs / x_tmp fields (projection_hip.hip, before init_ctx).
 cfd_status_t ensure_aux(hip_proj_ctx* c, bool need_rhs, bool need_xt)
     __attribute__((visibility("hidden")));

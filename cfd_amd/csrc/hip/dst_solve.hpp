@@ -66,8 +66,10 @@ constexpr int DST_XK = 64;   // k_dst_x: columns of X staged per chunk
 constexpr int DST_XP = 66;   // LDS row pitch: conflict-free fragment reads
 
 // Workgroup = 4 waves on one 64-row tile of the output and 4 adjacent
-// 16-column tiles (the waves share the table loads through the L1).
-template <bool SCALE>
+// 16-column tiles (the waves share the table loads through the L1). COS (with
+// SCALE): the cosine solve's scaling (dct_solve.hpp), a plain division by the
+// eigenvalue sum with the zero mode written as 0.0 and never divided.
+template <bool SCALE, bool COS = false>
 static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
                                                             const double* __restrict__ S,
                                                             const double* __restrict__ in,
@@ -106,7 +108,12 @@ static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
             const int a = a0 + 16 * m + kq + 4 * r;
             if (a >= g.n) continue;
             double v = acc[m][r];
-            if (SCALE) {
+            if (SCALE && COS) {
+                double lam = (sc.ea[a] * sc.ha) + (sc.ec[col] * sc.hc);
+                if (sc.eb) lam += sc.eb[q] * sc.hb;
+                const bool zero_mode = (a == 0) && (col == 0) && (!sc.eb || q == 0);
+                v = zero_mode ? 0.0 : v / lam;
+            } else if (SCALE) {
                 double lam = (sc.ea[a] * sc.ha) + (sc.ec[col] * sc.hc);
                 if (sc.eb) lam += sc.eb[q] * sc.hb;
                 v *= sc.norm / lam;
@@ -118,8 +125,9 @@ static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
 
 // Workgroup = 4 waves on 32 lines (consecutive j of one plane) x 256 output
 // columns, 64 per wave. FORM_B: the input is b = -rhs + (frozen boundary
-// neighbours of xb) / h^2, formed on the load (in = rhs).
-template <bool FORM_B>
+// neighbours of xb) / h^2, formed on the load (in = rhs). NEG (without
+// FORM_B): the input is -in, with no boundary terms (dct_solve.hpp).
+template <bool FORM_B, bool NEG = false>
 static __global__ __launch_bounds__(256) void k_dst_x(DstRows g, const double* __restrict__ S,
                                                       const double* __restrict__ in,
                                                       const double* __restrict__ xb,
@@ -160,6 +168,8 @@ static __global__ __launch_bounds__(256) void k_dst_x(DstRows g, const double* _
                         if (kq == 0) v += xb[idx - g.ps] * L.inv_dz2;
                         if (kq == g.nk - 1) v += xb[idx + g.ps] * L.inv_dz2;
                     }
+                } else if (NEG) {
+                    v = -in[idx];
                 } else {
                     v = in[idx];
                 }
@@ -243,44 +253,34 @@ static cfd_status_t dst_tables_of(hip_proj_ctx* c, DstTabs* T) {
     return CFD_SUCCESS;
 }
 
-// One unnormalised DST-I pass of the interior along `axis` (0 x, 1 y, 2 z):
-// in -> out (distinct fields). form_b (axis 0): the input is b formed from
-// in = rhs and the shell of xb. sc (axes 1, 2): the eigenvalue scaling on the
-// store.
-static void dst_pass(hip_proj_ctx* c, const DstTabs& T, int axis, const double* in, double* out,
-                     const DstScale* sc = nullptr, const double* xb = nullptr,
-                     const Lap* L = nullptr) {
+// The launch geometry of the x pass (table pitch np) and of a strided pass
+// along axis 1 (y) or 2 (z) with n points; shared with dct_solve.hpp
+static DstRows dst_rows_geo(const hip_proj_ctx* c, int np) {
     const bool is3d = c->nz > 1;
-    const int k0 = is3d ? 1 : 0;
-    const int nk = is3d ? (int)c->nz - 2 : 1;
-    if (axis == 0) {
-        DstRows g;
-        g.n = (int)c->nx - 2;
-        g.nj = (int)c->ny - 2;
-        g.nk = nk;
-        g.k0 = k0;
-        g.px = c->px;
-        g.ps = c->ps;
-        g.np = T.tx->np;
-        g.tiles_j = (g.nj + DST_XR - 1) / DST_XR;
-        g.tiles_a = (g.n + 255) / 256;
-        const dim3 grid((unsigned)(g.tiles_a * g.tiles_j * g.nk));
-        if (xb)
-            klaunch(c, k_dst_x<true>, grid, dim3(256), g, T.tx->S, in, xb, out, *L, is3d ? 1 : 0);
-        else
-            klaunch(c, k_dst_x<false>, grid, dim3(256), g, T.tx->S, in, nullptr, out, Lap{}, 0);
-        return;
-    }
-    const DstTable* t = (axis == 1) ? T.ty : T.tz;
+    DstRows g;
+    g.n = (int)c->nx - 2;
+    g.nj = (int)c->ny - 2;
+    g.nk = is3d ? (int)c->nz - 2 : 1;
+    g.k0 = is3d ? 1 : 0;
+    g.px = c->px;
+    g.ps = c->ps;
+    g.np = np;
+    g.tiles_j = (g.nj + DST_XR - 1) / DST_XR;
+    g.tiles_a = (g.n + 255) / 256;
+    return g;
+}
+
+static DstAxis dst_axis_geo(const hip_proj_ctx* c, int axis, int n, int np) {
+    const bool is3d = c->nz > 1;
     DstAxis g;
-    g.n = t->n;
+    g.n = n;
     g.nc = (int)c->nx - 2;
-    g.np = t->np;
+    g.np = np;
     if (axis == 1) {
-        g.nb = nk;
+        g.nb = is3d ? (int)c->nz - 2 : 1;
         g.sa = c->px;
         g.sb = c->ps;
-        g.off0 = (long long)k0 * c->ps + c->px + 1;
+        g.off0 = (long long)(is3d ? 1 : 0) * c->ps + c->px + 1;
     } else {
         g.nb = (int)c->ny - 2;
         g.sa = c->ps;
@@ -289,6 +289,28 @@ static void dst_pass(hip_proj_ctx* c, const DstTabs& T, int axis, const double* 
     }
     g.tiles_a = g.np / DST_TA;
     g.tiles_c = (g.nc + 63) / 64;
+    return g;
+}
+
+// One unnormalised DST-I pass of the interior along `axis` (0 x, 1 y, 2 z):
+// in -> out (distinct fields). form_b (axis 0): the input is b formed from
+// in = rhs and the shell of xb. sc (axes 1, 2): the eigenvalue scaling on the
+// store.
+static void dst_pass(hip_proj_ctx* c, const DstTabs& T, int axis, const double* in, double* out,
+                     const DstScale* sc = nullptr, const double* xb = nullptr,
+                     const Lap* L = nullptr) {
+    const bool is3d = c->nz > 1;
+    if (axis == 0) {
+        const DstRows g = dst_rows_geo(c, T.tx->np);
+        const dim3 grid((unsigned)(g.tiles_a * g.tiles_j * g.nk));
+        if (xb)
+            klaunch(c, k_dst_x<true>, grid, dim3(256), g, T.tx->S, in, xb, out, *L, is3d ? 1 : 0);
+        else
+            klaunch(c, k_dst_x<false>, grid, dim3(256), g, T.tx->S, in, nullptr, out, Lap{}, 0);
+        return;
+    }
+    const DstTable* t = (axis == 1) ? T.ty : T.tz;
+    const DstAxis g = dst_axis_geo(c, axis, t->n, t->np);
     const dim3 grid((unsigned)(g.tiles_c * g.tiles_a * g.nb));
     if (sc) klaunch(c, k_dst_strided<true>, grid, dim3(256), g, t->S, in, out, *sc);
     else klaunch(c, k_dst_strided<false>, grid, dim3(256), g, t->S, in, out, DstScale{});

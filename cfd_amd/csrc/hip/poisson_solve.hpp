@@ -1,7 +1,7 @@
 // poisson_solve.hpp -- the pressure solvers of the device context that are
 // compiled with projection_hip.hip (CG in its textbook and single-reduction
-// forms, BiCGSTAB, and through dst_solve.hpp the direct sine-transform solve)
-// with their launch wrappers. The relaxation methods are a unit of their own,
+// forms, BiCGSTAB, and through dst_solve.hpp / dct_solve.hpp the direct sine-
+// and cosine-transform solves) with their launch wrappers. The relaxation methods are a unit of their own,
 // relax_solve.hip; the polled device loop all share is poll.hpp. Host code
 // only; private to projection_hip.hip.
 #pragma once
@@ -471,3 +471,5 @@ static cfd_status_t bicgstab_solve(hip_proj_ctx* c, double dx, double dy, double
 
 // the direct sine-transform solver: uses ensure_aux and the poll helpers
 #include "dst_solve.hpp"
+// the direct cosine-transform solver: the same passes with cosine tables
+#include "dct_solve.hpp"

@@ -149,6 +149,11 @@ static void free_ctx(hip_proj_ctx* c) {
         if (t.S) hipFree(t.S);
         if (t.e) hipFree(t.e);
     }
+    for (const DctTable& t : c->dct_tabs) {
+        if (t.Q) hipFree(t.Q);
+        if (t.Qt) hipFree(t.Qt);
+        if (t.e) hipFree(t.e);
+    }
     for (hipEvent_t e : c->dst_ev)
         if (e) hipEventDestroy(e);
     if (c->partials) hipFree(c->partials);
@@ -792,9 +797,15 @@ void ctx_queue_max_T(hip_proj_ctx* c) {
                        c->stream, c->geo, c->T, c->red + 3, ks);
 }
 
-// The sine-transform solve works on whole z lines: a Z-slab context is
-// refused before anything is uploaded or launched (as BiCGSTAB's refusals).
+// The sine- and cosine-transform solves work on whole z lines: a Z-slab
+// context is refused before anything is uploaded or launched (as BiCGSTAB's
+// refusals).
 static cfd_status_t dst_refuse_slab(const hip_proj_ctx* c, int method) {
+    if (method == HIP_POISSON_DCT && dist(c)) {
+        set_err(CFD_ERROR_UNSUPPORTED,
+                "projection_hip: the DCT pressure solve runs on one device, not on Z-slabs");
+        return CFD_ERROR_UNSUPPORTED;
+    }
     if (method != HIP_POISSON_DST || !dist(c)) return CFD_SUCCESS;
     set_err(CFD_ERROR_UNSUPPORTED,
             "projection_hip: the DST pressure solve runs on one device, not on Z-slabs");
@@ -900,6 +911,9 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
         int maxit = c->cfg.poisson_max_iter;
         if (method == HIP_POISSON_DST)
             ps = dst_solve(c, dx, dy, dz, c->cfg.poisson_tolerance,
+                           c->cfg.poisson_abs_tolerance);
+        else if (method == HIP_POISSON_DCT)
+            ps = dct_solve(c, dx, dy, dz, c->cfg.poisson_tolerance,
                            c->cfg.poisson_abs_tolerance);
         else
             ps = relax_solve(c, method, dx, dy, dz, c->cfg.poisson_tolerance,
@@ -1204,6 +1218,12 @@ cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* c, int method, double* x,
         }
     }
     ST_TRY(dst_refuse_slab(c, method));
+    if (method == HIP_POISSON_DCT && bc_mode != HIP_POISSON_BC_NEUMANN) {
+        // the cosine transform diagonalises the Neumann problem only
+        set_err(CFD_ERROR_UNSUPPORTED,
+                "hip_proj_poisson_solve_ex: the DCT solve takes BC_NEUMANN only");
+        return CFD_ERROR_UNSUPPORTED;
+    }
     HIP_TRY(hipSetDevice(c->device));
     if (bc_mode == HIP_POISSON_BC_FIXED) {
         if (!c->bcfix) ST_TRY(dalloc(c, &c->bcfix, field_elems(c)));
@@ -1252,6 +1272,8 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
         s = bicgstab_solve(c, dx, dy, dz, rel, abs_tol, maxit, ci);
     } else if (method == HIP_POISSON_DST) {
         s = dst_solve(c, dx, dy, dz, rel, abs_tol);
+    } else if (method == HIP_POISSON_DCT) {
+        s = dct_solve(c, dx, dy, dz, rel, abs_tol);
     } else {
         s = relax_solve(c, method, dx, dy, dz, rel, abs_tol, maxit, ci, omega);
     }
@@ -1261,8 +1283,8 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (stats) {
         *stats = c->pstats;
-        // the direct solve reports its device time (events around the solve)
-        if (method != HIP_POISSON_DST) stats->elapsed_time_ms = 0.0;
+        // the direct solves report their device time (events around the solve)
+        if (method != HIP_POISSON_DST && method != HIP_POISSON_DCT) stats->elapsed_time_ms = 0.0;
     }
     return s;
 }
@@ -1291,6 +1313,38 @@ cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* c, double* field_host, int a
                                  c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
                                  c->stream));
     dst_pass(c, T, axis, c->pn, c->xt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(field_host, c->nx * sizeof(double), c->xt, c->px * sizeof(double),
+                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CFD_SUCCESS;
+}
+
+cfd_status_t hip_proj_dct_transform(hip_proj_ctx_t* c, double* field_host, int axis,
+                                    int inverse) {
+    GroupHostLock hl_(c);
+    if (!c || !field_host) return CFD_ERROR_INVALID;
+    if (axis < 0 || axis > 2) {
+        set_err(CFD_ERROR_INVALID, "hip_proj_dct_transform: axis must be 0 (x), 1 (y) or 2 (z)");
+        return CFD_ERROR_INVALID;
+    }
+    if (axis == 2 && c->nz == 1) {
+        set_err(CFD_ERROR_INVALID, "hip_proj_dct_transform: a 2-D context has no z axis");
+        return CFD_ERROR_INVALID;
+    }
+    ST_TRY(dst_refuse_slab(c, HIP_POISSON_DCT));
+    c->resident = 0;  // the transform runs in the step's pressure buffers
+    HIP_TRY(hipSetDevice(c->device));
+    ST_TRY(ensure_aux(c, false, true));
+    DctTabs T;
+    ST_TRY(dct_tables_of(c, &T));
+    // as hip_proj_dst_transform: the input goes to both fields
+    for (double* d : {c->pn, c->xt})
+        HIP_TRY(hipMemcpy2DAsync(d, c->px * sizeof(double), field_host, c->nx * sizeof(double),
+                                 c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
+                                 c->stream));
+    dct_pass(c, T, axis, inverse != 0, c->pn, c->xt);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2DAsync(field_host, c->nx * sizeof(double), c->xt, c->px * sizeof(double),
                              c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,

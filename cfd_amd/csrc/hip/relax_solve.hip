@@ -42,6 +42,13 @@ static cfd_status_t residual_linf(hip_proj_ctx* c, const double* x, const ResCoe
     return CFD_SUCCESS;
 }
 
+cfd_status_t relax_residual_linf(hip_proj_ctx* c, const double* x, double dx, double dy,
+                                 double dz, double* out) {
+    // relax_solve's coefficients
+    const ResCoef rc{dx * dx, dy * dy, (dz > 0.0) ? (1.0 / (dz * dz)) : 0.0};
+    return residual_linf(c, x, rc, out);
+}
+
 // One k_rb1 sweep on one device (3-D): xi -> xo (one RB-SOR iteration with
 // its Neumann shell when neu_fold), the L-inf residual of xi decided on `st`
 // as sweep `it` of the fused loop.

@@ -92,6 +92,11 @@ static cfd_status_t get_ctx(ns_solver_t* solver, const grid* g, hip_proj_ctx_t**
         if (pm && strcmp(pm, "dst") == 0 && solver->name &&
             strcmp(solver->name, NS_SOLVER_TYPE_PROJECTION_HIP) == 0)
             cfg.poisson_method = HIP_POISSON_DST;
+        /* CFD_HIP_POISSON=dct: likewise the direct cosine-transform method
+         * (HIP_POISSON_DCT), the Neumann problem of the relaxation solvers */
+        if (pm && strcmp(pm, "dct") == 0 && solver->name &&
+            strcmp(solver->name, NS_SOLVER_TYPE_PROJECTION_HIP) == 0)
+            cfg.poisson_method = HIP_POISSON_DCT;
         pc->ctx = hip_proj_create(g->nx, g->ny, g->nz, &cfg);
         if (!pc->ctx) return CFD_ERROR_UNSUPPORTED;
     }

@@ -60,7 +60,24 @@ typedef enum {
      * check_interval and omega are ignored; stats: iterations 1 (0 when the
      * initial residual is below absolute_tolerance), the 2-norm residuals of
      * CG, status by CG's rule on the final residual, elapsed_time_ms. */
-    HIP_POISSON_DST = 4
+    HIP_POISSON_DST = 4,
+    /* Direct solve of the Neumann problem by orthonormal type-II cosine
+     * transforms along each axis: the problem Red-Black SOR and Jacobi
+     * converge to (they apply the Neumann BC after every sweep, so every shell
+     * cell equals its interior neighbour). One device, BC_NEUMANN only
+     * (BC_NONE / BC_FIXED: CFD_ERROR_UNSUPPORTED), and a
+     * hip_proj_config_t.poisson_method of the projection step. No start BC;
+     * the Neumann shell is applied at the end. The zero mode is dropped: the
+     * interior mean of the result is zero, and for a right-hand side whose
+     * interior mean m is not zero (no solution exists) the result is the
+     * least-squares one with residual |m| in every cell, so the status is the
+     * one the iterations would reach; the pressure constant differs from
+     * theirs in every case (only grad p enters the step). max_iterations,
+     * check_interval and omega are ignored; stats: iterations 1 (0 when the
+     * initial residual is below absolute_tolerance and x is left untouched),
+     * the L-inf residuals and the status rule of the relaxation solvers,
+     * elapsed_time_ms. */
+    HIP_POISSON_DCT = 5
 } hip_poisson_method_t;
 
 /* Device/solver configuration (role of gpu_config_t, gpu_device.h:32-53). The
@@ -459,6 +476,18 @@ CFD_HIP_EXPORT cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* ctx, int m
  * (ends a resident run, like hip_proj_poisson_solve). */
 CFD_HIP_EXPORT cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* ctx, double* field_host,
                                                    int axis);
+
+/* One transform pass of HIP_POISSON_DCT on its own: the orthonormal type-II
+ * cosine transform of the interior of field_host along axis 0 (x), 1 (y) or
+ * 2 (z), in place,
+ *   y[a] = w_a sum_b cos(pi a (2 b + 1) / (2 n)) x[b],  w_0 = sqrt(1/n), w_a = sqrt(2/n),
+ * over the n interior cells of every line of that axis, or with inverse != 0
+ * its transpose (the type-III transform, its inverse); boundary cells are
+ * left as they are. CFD_ERROR_INVALID for another axis and for axis 2 on a
+ * 2-D context, CFD_ERROR_UNSUPPORTED on a Z-slab context. Uses the solve's
+ * work fields (ends a resident run, like hip_proj_poisson_solve). */
+CFD_HIP_EXPORT cfd_status_t hip_proj_dct_transform(hip_proj_ctx_t* ctx, double* field_host,
+                                                   int axis, int inverse);
 
 /* ---- Z-slab multi-GPU ------------------------------------------------------
  * The reference runs one device per simulation (solver_projection_gpu.cu has

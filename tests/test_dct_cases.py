@@ -1,0 +1,362 @@
+"""The direct cosine-transform pressure solve on the CPU: the numpy float64
+model of tests/dct_cases.py (the algorithm of cfd_amd/csrc/hip/dct_solve.hpp)
+against the oracle's RB-SOR and Jacobi run to 1e-15 on every shape of the
+table; the incompatible right-hand side; the model's stats rules; planted
+bugs; the public surface; the host table builder under ASan + UBSan; and the
+proof that the step fields of tests/test_gpu_dct.py give a compatible pressure
+problem.
+
+The largest deviation printed by test_model_matches_tight_relaxation, times
+100, is dct_cases.DCT_BAR, the bar of the device tests.
+"""
+import ctypes as C
+import os
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from cfd_amd import _abi as A
+from cfd_amd import _native, api
+from oracle import oracle
+from tests import dct_cases as K
+
+ROOT = Path(__file__).resolve().parents[1]
+HOST = ROOT / "cfd_amd" / "csrc" / "host"
+SHAPE_IDS = [K.sid(s) for s in K.SHAPE_LIST]
+
+
+def test_model_matches_tight_relaxation():
+    worst = {"redblack": 0.0, "jacobi": 0.0}
+    for shape in K.SHAPE_LIST:
+        m = K.model(shape)
+        assert (m.rc, m.status, m.iterations) == (A.CFD_SUCCESS, A.POISSON_CONVERGED, 1)
+        for method in worst:
+            if method == "jacobi" and max(shape) > K.JACOBI_MAX_EXTENT:
+                continue
+            rc, status, its, ref = K.tight_relax(shape, method)
+            assert (rc, status) == (A.CFD_SUCCESS, A.POISSON_CONVERGED), (shape, method, its)
+            dev = K.rel_dev(m.x, ref)
+            worst[method] = max(worst[method], dev)
+            print(f"DCT model {K.sid(shape)} {method}: deviation {dev:.3e} (iterations {its})")
+            assert dev <= K.DCT_BAR, (shape, method, dev)
+    big = max(worst.values())
+    print(f"DCT model: largest deviation RB-SOR {worst['redblack']:.3e}, Jacobi "
+          f"{worst['jacobi']:.3e}; x 100 = {100 * big:.3e}")
+    # the bar is the measured value x 100, written beside it
+    assert K.DCT_BAR == pytest.approx(100 * K.DCT_MEASURED, rel=1e-12)
+
+
+def test_tight_tolerance_is_the_tightest_power_of_ten():
+    """TIGHT_TOL converges on every shape (the test above); a tenth of it does
+    not: the oracle's RB-SOR stalls at ten times the iterations TIGHT_TOL took
+    on one of the 2-D shapes."""
+    assert K.TIGHT_TOL == 1e-15
+    stalled = []
+    for shape in K.SHAPE_LIST:
+        if shape[2] > 1:
+            continue
+        good, _, x0 = K.inputs(shape)
+        x = np.array(x0)
+        cap = 10 * max(100, K.tight_relax(shape)[2])
+        prm = oracle.poisson_params(tolerance=K.TIGHT_TOL / 10, absolute_tolerance=1e-300,
+                                    max_iterations=cap)
+        s, st = oracle.redblack_solve(x, np.ascontiguousarray(good), *K.spacing(shape), prm)
+        if st.status != A.POISSON_CONVERGED:
+            stalled.append(shape)
+    print(f"DCT: RB-SOR at {K.TIGHT_TOL / 10:g} stalls on {stalled}")
+    assert stalled
+
+
+@pytest.mark.parametrize("shape", K.SHAPE_LIST, ids=SHAPE_IDS)
+def test_incompatible_input(shape):
+    _, bad, x0 = K.inputs(shape)
+    d = K.spacing(shape)
+    m = K.model(shape, "incompatible")
+    mean = float(np.mean(bad[K.interior(bad.shape)]))
+    # the least-squares residual is the mean in every cell
+    assert abs(m.final_residual - abs(mean)) <= 1e-9 * abs(mean), (m.final_residual, mean)
+    thresh = max(1e-6 * m.initial_residual, 1e-10)
+    want = A.POISSON_MAX_ITER if abs(mean) >= thresh else A.POISSON_CONVERGED
+    assert m.status == want and m.iterations == 1
+    assert m.rc == (A.CFD_ERROR_MAX_ITER if want == A.POISSON_MAX_ITER else A.CFD_SUCCESS)
+    print(f"DCT incompatible {K.sid(shape)}: |mean rhs| {abs(mean):.3e} threshold {thresh:.3e} "
+          f"status {m.status}")
+    if max(shape) <= K.LIMIT_MAX_EXTENT:
+        rc, status, its, ref = K.jacobi_limit(shape)
+        assert its >= K.LIMIT_ITERATIONS and status == A.POISSON_MAX_ITER
+        dev = K.rel_dev(m.x, ref)
+        print(f"DCT incompatible {K.sid(shape)}: model - Jacobi limit {dev:.3e}")
+        assert dev <= K.DCT_BAR, dev
+
+
+def test_incompatible_status_goes_both_ways():
+    """The table holds right-hand sides on both sides of the threshold at a
+    tolerance of the test's choosing, so the rule above is not vacuous."""
+    seen = set()
+    for shape in K.SHAPE_LIST:
+        _, bad, x0 = K.inputs(shape)
+        mean = abs(float(np.mean(bad[K.interior(bad.shape)])))
+        for tol in (1e-6, 1e-1):
+            m = K.model_solve(x0, bad, K.spacing(shape), tolerance=tol)
+            thresh = max(tol * m.initial_residual, 1e-10)
+            assert (m.status == A.POISSON_MAX_ITER) == (mean >= thresh), (shape, tol)
+            seen.add(m.status)
+    assert seen == {A.POISSON_CONVERGED, A.POISSON_MAX_ITER}
+
+
+@pytest.mark.parametrize("shape", K.SHAPE_LIST, ids=SHAPE_IDS)
+def test_model_stats(shape):
+    good, bad, x0 = K.inputs(shape)
+    d = K.spacing(shape)
+    m = K.model(shape)
+    # the initial residual is solve_common's, bit for bit, with no start BC
+    for rhs in (good, bad):
+        assert K.residual_linf(np.array(x0), rhs, d) == K.oracle_initial_residual(x0, rhs, d)
+    assert m.initial_residual == K.oracle_initial_residual(x0, good, d)
+    assert m.final_residual < 1e-9 * m.initial_residual
+    # an unreachable tolerance: MAX_ITER with the same x
+    u = K.model_solve(x0, good, d, tolerance=1e-30, absolute_tolerance=1e-300)
+    if m.final_residual > 0.0:
+        assert (u.rc, u.status, u.iterations) == (A.CFD_ERROR_MAX_ITER, A.POISSON_MAX_ITER, 1)
+    assert np.array_equal(u.x, m.x) and u.final_residual == m.final_residual
+    # zero right-hand side from a constant field: the early exit, x untouched
+    z = K.model_solve(np.full_like(x0, 0.25), np.zeros_like(good), d)
+    assert (z.rc, z.status, z.iterations) == (A.CFD_SUCCESS, A.POISSON_CONVERGED, 0)
+    assert z.final_residual == z.initial_residual < 1e-10
+    assert np.array_equal(z.x, np.full_like(x0, 0.25))
+    # the zero mode is dropped: the interior mean is zero to rounding
+    for r in (m, K.model(shape, "incompatible")):
+        assert abs(np.mean(r.x[K.interior(r.x.shape)])) <= 1e-13 * np.max(np.abs(r.x))
+        again = r.x.copy()
+        oracle.poisson_apply_bc(again)
+        assert np.array_equal(again, r.x), "the Neumann BC applied again changes nothing"
+
+
+@pytest.mark.parametrize("bug", list(K.BUGS))
+def test_planted_bugs_show(bug):
+    exempt = [s for s in K.SHAPE_LIST if K.bug_exempt(bug, s)]
+    assert 2 * len(exempt) < len(K.SHAPE_LIST), exempt
+    which = "incompatible" if bug == "zero_div" else "compatible"
+    for shape in K.SHAPE_LIST:
+        good, bad, x0 = K.inputs(shape)
+        rhs = bad if which == "incompatible" else good
+        broken = K.model_solve(x0, rhs, K.spacing(shape), bug=bug).x
+        dev = K.rel_dev(broken, K.model(shape, which).x)
+        if shape in exempt:
+            assert dev == 0.0, (bug, shape, dev)
+        else:
+            assert dev > K.DCT_BAR, (bug, shape, dev)
+
+
+def test_transforms_are_orthonormal():
+    ns = sorted({v - 2 for s in K.SHAPE_LIST for v in K.extents(s)})
+    for n in ns:
+        Q = K.cos_matrix(n)
+        assert np.max(np.abs(Q @ Q.T - np.eye(n))) <= 1e-13, n
+        assert np.max(np.abs(Q.T @ Q - np.eye(n))) <= 1e-13, n
+    for shape in K.SHAPE_LIST:
+        _, _, x0 = K.inputs(shape)
+        sh = K.shell_mask(x0.shape)
+        for axis in range(len(K.extents(shape))):
+            back = K.transform(K.transform(np.array(x0), axis), axis, inverse=True)
+            assert np.allclose(back, x0, rtol=0, atol=1e-13)
+            assert np.array_equal(back[sh], x0[sh])
+
+
+def test_shape_table():
+    assert K.SHAPE_LIST[:-2] == K.D.SHAPE_LIST and K.SHAPE_LIST[-2:] == [(18, 17, 1), (10, 11, 12)]
+    for axis in range(3):
+        n = {s[axis] - 2 for s in K.SHAPE_LIST if axis < len(K.extents(s))}
+        assert any(v % 2 == 0 for v in n) and any(v % 2 == 1 and v > 1 for v in n), (axis, n)
+    assert all(d[0] != d[1] and (s[2] == 1 or d[1] != d[2])
+               for s in K.SHAPE_LIST for d in [K.spacing(s)])
+
+
+def test_surface():
+    """The method value, the entry point and the bindings; ABI version and the
+    timer count stay."""
+    hdr = (ROOT / "include" / "cfd_hip" / "projection_hip.h").read_text()
+    assert A.HIP_POISSON_DCT == 5 and "HIP_POISSON_DCT = 5" in hdr
+    assert A.HIP_POISSON_DST == 4 and "HIP_POISSON_DST = 4," in hdr
+    assert "cfd_status_t hip_proj_dct_transform(hip_proj_ctx_t* ctx, double* field_host," in hdr
+    assert "int axis, int inverse);" in hdr
+    assert "#define HIP_PROJ_ABI_VERSION 4" in hdr and "HIP_KT_COUNT = 21" in hdr
+    src = (ROOT / "cfd_amd" / "csrc" / "hip" / "projection_hip.hip").read_text()
+    assert "the DCT pressure solve runs on one device, not on Z-slabs" in src
+    plugin = (HOST / "projection_hip_plugin.c").read_text()
+    assert 'strcmp(pm, "dct") == 0' in plugin
+    hip = _native.hip()
+    assert hip.hip_proj_abi_version() == 4 and A.HIP_KT_COUNT == 21
+    assert hip.hip_proj_dct_transform.argtypes == [C.c_void_p, A.c_double_p, C.c_int, C.c_int]
+    assert callable(api.HipProjection.dct_transform)
+    assert hip.hip_proj_dct_transform(None, None, 0, 0) == A.CFD_ERROR_INVALID
+
+
+# ---------------------------------------------------------------------------
+# the step inputs of tests/test_gpu_dct.py, with the oracle alone
+# ---------------------------------------------------------------------------
+def _oracle_step(shape, fill):
+    nx, ny, nz = shape
+    g = api.Grid(nx, ny, nz, 0.0, K.D.BOX[0], 0.0, K.D.BOX[1], 0.0, K.D.BOX[2] if nz > 1 else 0.0)
+    f = api.FlowField(nx, ny, nz)
+    for k, v in K.step_fields(shape, fill).items():
+        getattr(f, k)[...] = v
+    f.rho[...] = 1.0
+    f.T[...] = 300.0
+    prm = api.validation_params(K.STEP_DT, K.STEP_NU)
+    oracle.set_projection_poisson_params(oracle.poisson_params(**K.STEP_PARAMS))
+    try:
+        s, _, its = oracle.projection_step(f, g, prm, A.ORACLE_POISSON_REDBLACK)
+    finally:
+        oracle.set_projection_poisson_params(None)
+    return s, oracle.last_poisson_stats(), its
+
+
+@pytest.mark.parametrize("shape", K.STEP_SHAPES, ids=K.sid)
+def test_step_fields_give_a_compatible_problem(shape):
+    """Velocities that vanish on the three outermost interior layers: the
+    oracle's RB-SOR step reaches 1e-12. Filling the interior: it stalls at the
+    cap (the right-hand side's interior mean is not zero)."""
+    s, st, its = _oracle_step(shape, fill=False)
+    print(f"DCT step inputs {K.sid(shape)}: RB-SOR at {K.STEP_TOL:g}: {st.iterations} iterations")
+    assert s == A.CFD_SUCCESS and st.status == A.POISSON_CONVERGED
+    assert st.iterations < K.STEP_PARAMS["max_iterations"]
+    s, st, its = _oracle_step(shape, fill=True)
+    assert st.status == A.POISSON_MAX_ITER and st.iterations >= K.STEP_PARAMS["max_iterations"]
+
+
+def test_cavity_step_is_incompatible():
+    """The right-hand side of the cavity step of tests/test_gpu_dct.py, rebuilt
+    from the oracle's one-iteration step: its L-inf residual against the
+    step's initial p is the one the oracle's solver saw, its interior mean is
+    far above the default threshold, and the oracle's RB-SOR stalls on it."""
+    rhs, res0 = K.cavity_rhs()
+    fields = K.cavity_fields()
+    d = K.spacing(K.CAVITY_SHAPE)
+    m = K.model_solve(fields["p"], rhs, d)
+    assert abs(m.initial_residual - res0) <= 1e-12 * res0
+    mean = abs(float(np.mean(rhs[K.interior(rhs.shape)])))
+    assert mean > 100 * max(1e-6 * res0, 1e-10)
+    assert (m.rc, m.status) == (A.CFD_ERROR_MAX_ITER, A.POISSON_MAX_ITER)
+    assert abs(m.final_residual - mean) <= 1e-9 * mean
+    x = np.array(fields["p"])
+    s, st = oracle.redblack_solve(x, np.ascontiguousarray(rhs), *d,
+                                  oracle.poisson_params(max_iterations=3000))
+    assert st.status == A.POISSON_MAX_ITER
+
+
+# ---------------------------------------------------------------------------
+# the host table builder as a program of its own, under ASan + UBSan
+# ---------------------------------------------------------------------------
+SAN_DRIVER = r"""
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include "dst_tables.h"
+
+#define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAIL %s:%d %s (n = %zu)\n", __FILE__, __LINE__, #c, n); return 1; } } while (0)
+
+int main(void) {
+    const size_t ns[] = {1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 259};
+    for (size_t q = 0; q < sizeof ns / sizeof ns[0]; q++) {
+        const size_t n = ns[q], np = dst_table_pitch(n);
+        CHECK(np >= n && np % 64 == 0 && np < n + 64);
+        /* heap blocks of exactly the documented sizes */
+        double* Q = (double*)malloc(np * np * sizeof(double));
+        double* Qt = (double*)malloc(np * np * sizeof(double));
+        double* e = (double*)malloc(n * sizeof(double));
+        CHECK(Q && Qt && e);
+        dct_fill_cos_tables(n, Q, Qt);
+        dct_fill_eigenvalues(n, e);
+        for (size_t a = 0; a < np; a++)
+            for (size_t b = 0; b < np; b++) {
+                const double v = Q[a * np + b];
+                CHECK(v == Qt[b * np + a]); /* the transpose, bit for bit */
+                if (a >= n || b >= n) CHECK(v == 0.0);
+                else {
+                    const double w = a == 0 ? sqrt(1.0 / (double)n) : sqrt(2.0 / (double)n);
+                    const double t = M_PI * (double)(a * (2 * b + 1) % (4 * n)) / (double)(2 * n);
+                    CHECK(fabs(v - w * cos(t)) < 1e-14);
+                }
+            }
+        /* Q Q^T = I, every row sum of its entries */
+        for (size_t a = 0; a < n; a++) {
+            double rowsum = 0.0;
+            for (size_t c = 0; c < n; c++) {
+                double s = 0.0;
+                for (size_t k = 0; k < n; k++) s += Q[a * np + k] * Qt[k * np + c];
+                CHECK(fabs(s - (a == c ? 1.0 : 0.0)) < 1e-13);
+                rowsum += s;
+            }
+            CHECK(fabs(rowsum - 1.0) < 1e-12);
+        }
+        CHECK(e[0] == 0.0);
+        for (size_t a = 1; a < n; a++) CHECK(e[a] > e[a - 1] && e[a] < 4.0);
+        free(Q);
+        free(Qt);
+        free(e);
+    }
+    printf("ok\n");
+    return 0;
+}
+"""
+
+
+def test_cos_table_builder_under_asan_ubsan(tmp_path):
+    src = tmp_path / "dct_drv.c"
+    src.write_text(SAN_DRIVER)
+    exe = tmp_path / "dct_drv"
+    cmd = ["gcc", "-std=gnu11", "-g", "-O1", "-fno-omit-frame-pointer",
+           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", f"-I{HOST}",
+           str(src), "-o", str(exe), "-lm"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    env.pop("LD_PRELOAD", None)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", (out.stdout + out.stderr)[-4000:]
+
+
+def test_model_tables_are_the_builders():
+    """The numpy tables of the model equal the C builder's, bit for bit (the
+    device tests then compare the kernels with the model on the same tables)."""
+    src = r"""
+#include <stdio.h>
+#include <stdlib.h>
+#include "dst_tables.h"
+int main(int argc, char** argv) {
+    const size_t n = (size_t)atoi(argv[1]), np = dst_table_pitch(n);
+    double* Q = (double*)malloc(np * np * sizeof(double));
+    double* Qt = (double*)malloc(np * np * sizeof(double));
+    double* e = (double*)malloc(n * sizeof(double));
+    dct_fill_cos_tables(n, Q, Qt);
+    dct_fill_eigenvalues(n, e);
+    fwrite(Q, sizeof(double), np * np, stdout);
+    fwrite(e, sizeof(double), n, stdout);
+    return 0;
+}
+"""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        c = Path(td) / "dump.c"
+        c.write_text(src)
+        exe = Path(td) / "dump"
+        r = subprocess.run(["gcc", "-std=gnu11", "-O1", f"-I{HOST}", str(c), "-o", str(exe), "-lm"],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        worst = 0.0
+        for n in (1, 2, 3, 16, 19, 65, 259):
+            raw = subprocess.run([str(exe), str(n)], capture_output=True, check=True).stdout
+            np_ = (n + 63) // 64 * 64
+            a = np.frombuffer(raw, dtype=np.float64)
+            Q = a[:np_ * np_].reshape(np_, np_)[:n, :n]
+            e = a[np_ * np_:]
+            # two long-double evaluations of the same reduced argument, each
+            # rounded once: equal but for a rare tie in the last place
+            worst = max(worst, float(np.max(np.abs(Q - K.cos_matrix(n)))),
+                        float(np.max(np.abs(e - K.eig(n)))))
+            assert np.max(np.abs(Q - K.cos_matrix(n))) <= 2.0 ** -52
+            assert np.max(np.abs(e - K.eig(n))) <= 2.0 ** -51
+        print(f"DCT tables: builder - model {worst:.3e}")
