@@ -10,14 +10,19 @@
 // ...), one 16-B load per resident field and pair. Rows start on 64-B
 // boundaries (px is a multiple of 8), so the pair that straddles nx is loaded
 // whole and its pad half is never folded into a result; pairs past nx are not
-// loaded at all. Per thread: min, max (fmin / fmax: NaN ignored) and sum, in
-// that walk order, of each resident field among u, v, w, p, rho, T and, on
-// request, of sqrt((u*u) + (v*v) + (w*w)) (the reference's expression; the
-// file is compiled with -ffp-contract=off), which an optional output array
-// receives with non-temporal 16-B stores in the padded layout.
+// loaded at all. Per thread: min, max (fmin / fmax over the non-NaN values),
+// sum and the first-zero key (ds_comb), in that walk order, of each resident
+// field among u, v, w, p, rho, T and, on request, of
+// sqrt((u*u) + (v*v) + (w*w)) (the reference's expression; the file is
+// compiled with -ffp-contract=off), which an optional output array receives
+// with non-temporal 16-B stores in the padded layout. The lane that holds
+// cell 0 also stores each quantity's cell-0 value beside the totals. From
+// these the host states the reference's sequential `<` / `>` loop (ds_stats):
+// a NaN in cell 0 is min and max, bit for bit; a zero extreme has the sign of
+// the zero with the lowest packed index.
 //
-// Reduction (device_util.hpp's scheme, 21 scalars): the per-thread order above, a
-// fixed 64-lane shuffle tree, the four waves in order, one record of 21
+// Reduction (device_util.hpp's scheme, 28 scalars): the per-thread order above, a
+// fixed 64-lane shuffle tree, the four waves in order, one record of 28
 // values per workgroup stored by one lane with agent-scope relaxed
 // (write-through) stores, s_waitcnt vmcnt(0), a ticket; the last workgroup
 // reads every record with agent-scope loads and combines record b of each
@@ -41,11 +46,16 @@ namespace {
 constexpr int DS_NT = 256;       // threads per workgroup
 constexpr int DS_WAVES = DS_NT / 64;
 constexpr int DS_NF = 7;         // u v w p rho T |vel|
-constexpr int DS_NS = 3 * DS_NF; // min, max, sum of each
-constexpr int DS_MAX_WG = 1024;  // 4 per CU: the last workgroup reads 21 x 1024 values
+constexpr int DS_NK = 4;         // min, max, sum, first-zero key of each
+constexpr int DS_NS = DS_NK * DS_NF;
+constexpr int DS_MAX_WG = 1024;  // 4 per CU: the last workgroup reads 28 x 1024 values
 constexpr size_t DS_TOT = (size_t)DS_NS * DS_MAX_WG;  // totals after the records
-constexpr size_t DS_TICKET = DS_TOT + 32;             // the ticket word
+constexpr size_t DS_CELL0 = DS_TOT + DS_NS;           // cell 0 of each quantity after the totals
+constexpr size_t DS_TICKET = DS_TOT + 40;             // the ticket word
 constexpr size_t DS_ELEMS = DS_TICKET + 8;
+constexpr int DS_NOUT = DS_NS + DS_NF;                // what the host reads back
+static_assert(DS_CELL0 + DS_NF <= DS_TICKET, "the cell-0 values end before the ticket");
+constexpr unsigned long long DS_NO_ZERO = ~0ULL;      // key of a field without a zero
 
 struct DsArgs {
     const double* f[6];  // u v w p rho T; nullptr: not part of this pass
@@ -54,10 +64,19 @@ struct DsArgs {
     long long px, ps;
 };
 
-// scalar s of a record: field s / 3, kind s % 3 (0 min, 1 max, 2 sum)
+// scalar s of a record: field s / 4, kind s % 4 (0 min, 1 max, 2 sum, 3 the
+// first-zero key). The key is 2 * (k nx ny + j nx + i) + sign bit of the zero
+// with the lowest packed index, DS_NO_ZERO without one; it travels through the
+// record as the 64 bits of a double (moves only) and combines as an unsigned min.
 template <int KIND>
 __device__ __forceinline__ double ds_comb(double a, double b) {
-    return KIND == 0 ? fmin(a, b) : (KIND == 1 ? fmax(a, b) : a + b);
+    if constexpr (KIND == 3) {
+        const unsigned long long x = (unsigned long long)__double_as_longlong(a);
+        const unsigned long long y = (unsigned long long)__double_as_longlong(b);
+        return __longlong_as_double((long long)(x < y ? x : y));
+    } else {
+        return KIND == 0 ? fmin(a, b) : (KIND == 1 ? fmax(a, b) : a + b);
+    }
 }
 template <int KIND>
 __device__ __forceinline__ double ds_wave(double v) {
@@ -68,28 +87,49 @@ __device__ __forceinline__ double ds_wave(double v) {
 template <int KIND>
 __device__ __forceinline__ double ds_ident() {
     return KIND == 0 ? __longlong_as_double(0x7FF0000000000000LL)
-                     : (KIND == 1 ? __longlong_as_double((long long)0xFFF0000000000000ULL) : 0.0);
+           : KIND == 1 ? __longlong_as_double((long long)0xFFF0000000000000ULL)
+           : KIND == 2 ? 0.0 : __longlong_as_double((long long)DS_NO_ZERO);
 }
 
 struct DsAcc {
     double mn, mx, sm;
-    __device__ __forceinline__ void add(double v) {
+    unsigned long long zk;
+    __device__ __forceinline__ void fold(double v) {
         mn = fmin(mn, v);
         mx = fmax(mx, v);
         sm += v;
+    }
+    __device__ __forceinline__ void zero(double v, unsigned long long cell) {
+        const unsigned long long key =
+            (cell << 1) | ((unsigned long long)__double_as_longlong(v) >> 63);
+        zk = key < zk ? key : zk;
+    }
+    // One 16-B pair; cell: the packed index k nx ny + j nx + i of v.x; two: v.y
+    // is a cell, not pad. The key work sits behind a branch the whole wave
+    // takes together, so a pair without a zero pays two compares for it.
+    __device__ __forceinline__ void add(double2 v, bool two, unsigned long long cell) {
+        fold(v.x);
+        if (two) fold(v.y);
+        const bool zx = v.x == 0.0, zy = two && v.y == 0.0;
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(zx || zy) != 0, 0)) {
+            if (zx) zero(v.x, cell);
+            if (zy) zero(v.y, cell + 1);
+        }
     }
 };
 
 template <int S>
 __device__ __forceinline__ double ds_get(const DsAcc (&a)[DS_NF]) {
-    return S % 3 == 0 ? a[S / 3].mn : (S % 3 == 1 ? a[S / 3].mx : a[S / 3].sm);
+    constexpr int K = S % DS_NK, F = S / DS_NK;
+    return K == 0 ? a[F].mn : K == 1 ? a[F].mx : K == 2 ? a[F].sm
+                                                       : __longlong_as_double((long long)a[F].zk);
 }
 
 // wave totals of scalar S .. DS_NS - 1 into sh[s][wave]
 template <int S>
 __device__ __forceinline__ void ds_wave_all(const DsAcc (&a)[DS_NF], double (*sh)[DS_WAVES]) {
     if constexpr (S < DS_NS) {
-        const double v = ds_wave<S % 3>(ds_get<S>(a));
+        const double v = ds_wave<S % DS_NK>(ds_get<S>(a));
         if ((threadIdx.x & 63) == 0) sh[S][threadIdx.x >> 6] = v;
         ds_wave_all<S + 1>(a, sh);
     }
@@ -101,25 +141,48 @@ __device__ __forceinline__ void ds_block_all(double (*sh)[DS_WAVES], double (&ou
     if constexpr (S < DS_NS) {
         double v = sh[S][0];
 #pragma unroll
-        for (int w = 1; w < DS_WAVES; ++w) v = ds_comb<S % 3>(v, sh[S][w]);
+        for (int w = 1; w < DS_WAVES; ++w) v = ds_comb<S % DS_NK>(v, sh[S][w]);
         out[S] = v;
         ds_block_all<S + 1>(sh, out);
     }
 }
 
-// last workgroup: records 0 .. nb - 1 of scalar S, thread-strided in index order
+// last workgroup: records 0 .. nb - 1 of scalar S, thread-strided in index
+// order (thread t folds b = t, t + 256, ... from the identity). The thread's
+// records of one field's DS_NK scalars are loaded together (one memory latency
+// per field, not one per record), then folded in that order.
+constexpr int DS_NB = DS_MAX_WG / DS_NT;  // records of a scalar per thread, at most
 template <int S>
+__device__ __forceinline__ void ds_grid_fold(const double (&x)[DS_NB], unsigned nb,
+                                             double (*sh)[DS_WAVES]) {
+    double v = ds_ident<S % DS_NK>();
+#pragma unroll
+    for (int i = 0; i < DS_NB; ++i)
+        if (threadIdx.x + i * DS_NT < nb) v = ds_comb<S % DS_NK>(v, x[i]);
+    v = ds_wave<S % DS_NK>(v);
+    if ((threadIdx.x & 63) == 0) sh[S][threadIdx.x >> 6] = v;
+}
+template <int F>
 __device__ __forceinline__ void ds_grid_all(const double* rec, unsigned nb,
                                             double (*sh)[DS_WAVES]) {
-    if constexpr (S < DS_NS) {
-        double v = ds_ident<S % 3>();
-        for (unsigned b = threadIdx.x; b < nb; b += DS_NT)
-            v = ds_comb<S % 3>(v, load_sc1(&rec[(size_t)S * nb + b]));
-        v = ds_wave<S % 3>(v);
-        if ((threadIdx.x & 63) == 0) sh[S][threadIdx.x >> 6] = v;
-        ds_grid_all<S + 1>(rec, nb, sh);
+    if constexpr (F < DS_NF) {
+        double x[DS_NK][DS_NB];
+#pragma unroll
+        for (int k = 0; k < DS_NK; ++k) {
+#pragma unroll
+            for (int i = 0; i < DS_NB; ++i) {
+                const unsigned b = threadIdx.x + i * DS_NT;  // past nb: record 0, not folded
+                x[k][i] = load_sc1(&rec[(size_t)(F * DS_NK + k) * nb + (b < nb ? b : 0u)]);
+            }
+        }
+        ds_grid_fold<F * DS_NK + 0>(x[0], nb, sh);
+        ds_grid_fold<F * DS_NK + 1>(x[1], nb, sh);
+        ds_grid_fold<F * DS_NK + 2>(x[2], nb, sh);
+        ds_grid_fold<F * DS_NK + 3>(x[3], nb, sh);
+        ds_grid_all<F + 1>(rec, nb, sh);
     }
 }
+static_assert(DS_NK == 4, "ds_grid_all folds four scalars per field");
 
 template <bool MAG>
 __global__ __launch_bounds__(DS_NT) void k_derived_stats(DsArgs a, double* rec, double* tot,
@@ -132,6 +195,7 @@ __global__ __launch_bounds__(DS_NT) void k_derived_stats(DsArgs a, double* rec, 
         acc[q].mn = ds_ident<0>();
         acc[q].mx = ds_ident<1>();
         acc[q].sm = 0.0;
+        acc[q].zk = DS_NO_ZERO;
     }
     const int lane = threadIdx.x & 63;
     const long long nrows = (long long)a.ny * a.nz;
@@ -140,8 +204,11 @@ __global__ __launch_bounds__(DS_NT) void k_derived_stats(DsArgs a, double* rec, 
          r += (long long)gridDim.x * DS_WAVES) {
         const long long k = r / a.ny, j = r - k * a.ny;
         const long long row = k * a.ps + j * a.px;
+        const unsigned long long cell0 = (unsigned long long)r * (unsigned long long)a.nx;
         for (int q = lane; q < npair; q += 64) {
             const long long idx = row + 2 * q;
+            const unsigned long long cell = cell0 + 2 * (unsigned)q;
+            const bool first = r == 0 && q == 0;  // this lane holds cell 0
             const bool two = 2 * q + 1 < a.nx;  // the pair's second cell is a cell, not pad
             double2 val[6];
 #pragma unroll
@@ -150,8 +217,8 @@ __global__ __launch_bounds__(DS_NT) void k_derived_stats(DsArgs a, double* rec, 
 #pragma unroll
             for (int f = 0; f < 6; ++f) {
                 if (a.f[f]) {
-                    acc[f].add(val[f].x);
-                    if (two) acc[f].add(val[f].y);
+                    acc[f].add(val[f], two, cell);
+                    if (first) tot[DS_NS + f] = val[f].x;
                 }
             }
             if (MAG) {
@@ -160,8 +227,8 @@ __global__ __launch_bounds__(DS_NT) void k_derived_stats(DsArgs a, double* rec, 
                                        (val[2].x * val[2].x));
                 const double my = sqrt((val[0].y * val[0].y) + (val[1].y * val[1].y) +
                                        (val[2].y * val[2].y));
-                acc[6].add(mx);
-                if (two) acc[6].add(my);
+                acc[6].add(make_double2(mx, my), two, cell);
+                if (first) tot[DS_NS + 6] = mx;
                 if (a.mag) {
                     d2x w = {mx, two ? my : 0.0};
                     __builtin_nontemporal_store(w, reinterpret_cast<d2x*>(a.mag + idx));
@@ -229,9 +296,10 @@ unsigned ds_grid(const hip_proj_ctx* c) {
                                                        DS_MAX_WG));
 }
 
-// One pass over the fields of `a`; tot[3 q .. 3 q + 2] = min, max, sum of
-// field q (valid for the fields in the pass, and for q = 6 with `mag`).
-cfd_status_t ds_run(hip_proj_ctx* c, const DsArgs& a, bool mag, double (&tot)[DS_NS]) {
+// One pass over the fields of `a`; tot[4 q .. 4 q + 3] = min, max, sum and
+// first-zero key of field q, tot[DS_NS + q] its cell 0 (valid for the fields
+// in the pass, and for q = 6 with `mag`).
+cfd_status_t ds_run(hip_proj_ctx* c, const DsArgs& a, bool mag, double (&tot)[DS_NOUT]) {
     if (!c->dstat) {
         if (dalloc(c, &c->dstat, DS_ELEMS) != CFD_SUCCESS) return CFD_ERROR_NOMEM;
     }
@@ -245,11 +313,23 @@ cfd_status_t ds_run(hip_proj_ctx* c, const DsArgs& a, bool mag, double (&tot)[DS
     return CFD_SUCCESS;
 }
 
-field_stats ds_stats(const double (&tot)[DS_NS], int q, double count) {
+// The reference's sequential loop (derived_fields.c:107-120): min and max
+// start at data[0] and move on strict `<` / `>`. A NaN in cell 0 therefore
+// stays in both; any other NaN is ignored; a zero extreme keeps the sign of
+// the first zero in index order (no later zero compares below or above it).
+field_stats ds_stats(const double (&tot)[DS_NOUT], int q, double count) {
     field_stats s;
-    s.min_val = tot[3 * q];
-    s.max_val = tot[3 * q + 1];
-    s.sum_val = tot[3 * q + 2];
+    const double first = tot[DS_NS + q];
+    if (first != first) {
+        s.min_val = s.max_val = first;
+    } else {
+        unsigned long long key;
+        memcpy(&key, &tot[DS_NK * q + 3], sizeof(key));
+        const double zero = (key & 1ULL) ? -0.0 : 0.0;
+        s.min_val = tot[DS_NK * q] == 0.0 ? zero : tot[DS_NK * q];
+        s.max_val = tot[DS_NK * q + 1] == 0.0 ? zero : tot[DS_NK * q + 1];
+    }
+    s.sum_val = tot[DS_NK * q + 2];
     s.avg_val = s.sum_val / count;
     return s;
 }
@@ -277,7 +357,7 @@ cfd_status_t ds_derived(hip_proj_ctx* c, int with_vel_mag, double rho0, derived_
     DsArgs a = ds_args(c);
     const double* fs[6] = {c->u, c->v, c->w, c->p, c->rho, c->T};
     for (int q = 0; q < 6; ++q) a.f[q] = fs[q];
-    double tot[DS_NS];
+    double tot[DS_NOUT];
     ST_TRY(ds_run(c, a, with_vel_mag != 0, tot));
     const double count = (double)(c->nx * c->ny * c->nz);
     field_stats* dst[6] = {&out->u_stats, &out->v_stats, &out->w_stats,
@@ -305,7 +385,7 @@ cfd_status_t hip_proj_field_statistics(hip_proj_ctx_t* c, int field_id, field_st
     HIP_TRY(hipSetDevice(c->device));
     DsArgs a = ds_args(c);
     a.f[0] = f;
-    double tot[DS_NS];
+    double tot[DS_NOUT];
     ST_TRY(ds_run(c, a, false, tot));
     *out = ds_stats(tot, 0, (double)(c->nx * c->ny * c->nz));
     return CFD_SUCCESS;
@@ -330,7 +410,7 @@ cfd_status_t hip_proj_velocity_magnitude(hip_proj_ctx_t* c, double* host) {
     a.f[1] = c->v;
     a.f[2] = c->w;
     a.mag = c->vmag;
-    double tot[DS_NS];
+    double tot[DS_NOUT];
     ST_TRY(ds_run(c, a, true, tot));
     HIP_TRY(hipMemcpy2DAsync(host, c->nx * sizeof(double), c->vmag, c->px * sizeof(double),
                              c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,

@@ -383,11 +383,13 @@ CFD_HIP_EXPORT cfd_status_t hip_proj_write_vtk(hip_proj_ctx_t* ctx, const char* 
  * None of these entries changes device state or ends a resident (dirty_faces)
  * run; single-device contexts only (Z-slab: CFD_ERROR_UNSUPPORTED). Additive:
  * no ABI version change, no kernel timer.
- *   min / max  ignore NaN (fmin / fmax); the reference's `<` / `>` loop does so
- *              for every element but data[0]. A field of NaNs only reports
- *              min = +inf, max = -inf. The sign of a zero min / max is
- *              unspecified (the reference's own depends on the element order).
- *   sum        a NaN or Inf in a field propagates into that field's sum. The
+ *   min / max  the reference's sequential loop, which starts both at data[0]
+ *              and moves them on strict `<` / `>`: if cell 0 is NaN, both are
+ *              that NaN's 64 bits; otherwise the least / greatest non-NaN
+ *              value, a zero extreme with the sign of the zero of lowest
+ *              packed index k*nx*ny + j*nx + i.
+ *   sum        a NaN in a field, or both infinities, make that field's sum NaN
+ *              (sign and payload unspecified); infinities of one sign, +-inf. The
  *              order is fixed (per thread, 64-lane tree, waves, workgroups in
  *              index order): bit-identical from run to run, equal to the
  *              reference's sequential sum up to rounding.

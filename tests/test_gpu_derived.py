@@ -9,6 +9,12 @@ sum and avg are the reference's bits; on real-valued fields
 |sum_dev - fsum(x)| <= n * 2^-53 * sum|x|, the worst-case bound of any
 summation order (derived, not measured; one dropped or doubled cell is orders
 of magnitude above it on these fields).
+
+The second half holds the entries to the contract of
+tests/derived_special_cases.py on NaN, signed-zero, inf and extreme fields
+(tests/golden/derived_special_cases.json): min and max as 64-bit patterns,
+sum and avg by their class, the magnitude cell by cell, the CSV files byte
+for byte.
 """
 import ctypes as C
 import json
@@ -22,6 +28,7 @@ from cfd_amd import _abi as A
 from cfd_amd import api
 from tests import cases
 from tests import derived_cases as K
+from tests import derived_special_cases as S
 from tests.special_values import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -347,3 +354,165 @@ def test_device_csv_files_match_byte_for_byte(record, hip_lib, tmp_path, name, m
         assert st.read_bytes() == want[f"statistics_mag{mag}"].encode()
     finally:
         ctx.close()
+
+
+# ---- NaN, signed zeros, infinities, extreme magnitudes -------------------------
+
+@pytest.fixture(scope="module")
+def special_record():
+    return json.loads((GOLDEN / S.JSON_FILE).read_text())
+
+
+@pytest.fixture(scope="module")
+def special_ctx(hip_lib):
+    """shape -> one context; a test loads all six fields of its case."""
+    cache = {}
+
+    def get(case, step=0):
+        shape = tuple(case["shape"])
+        if shape not in cache:
+            cache[shape] = api.HipProjection(*shape)
+        arrs = S.inputs(case, step)
+        for k in S.FIELDS:
+            cache[shape].set_field(FID[k], arrs[k])
+        return cache[shape], arrs
+
+    yield get
+    for ctx in cache.values():
+        ctx.close()
+
+
+def raw(s):
+    """{min, max, avg, sum} of a field_stats as uint64 patterns."""
+    names = [n.replace("_val", "") for n, _ in A.FieldStats._fields_]
+    assert sorted(names) == ["avg", "max", "min", "sum"]
+    return dict(zip(names, np.frombuffer(bytes(s), dtype=np.uint64).tolist()))
+
+
+def rec_bits(r, m):
+    return int(r[m], 16)
+
+
+def same_sum(x, y):
+    """Two sums / averages as patterns: both NaN, or the same bits."""
+    fx, fy = S.from_bits(x), S.from_bits(y)
+    return (math.isnan(fx) and math.isnan(fy)) or x == y
+
+
+@pytest.mark.parametrize("case", S.CASES, ids=lambda c: c["name"])
+def test_special_fields_against_the_record(special_record, special_ctx, case):
+    rec = special_record["cases"][case["name"]]
+    ctx, arrs = special_ctx(case)
+    d = ctx.derived_statistics(True, S.RHO0)
+    mag = ctx.velocity_magnitude()
+    assert_bits_equal(mag, S.magnitude(arrs), what=f"{case['name']}: velocity magnitude")
+    assert S.sha_nan_canonical(mag) == rec["vel_mag_sha256"]
+    if case["name"] == S.NPZ_CASE:
+        assert_bits_equal(mag, np.load(GOLDEN / S.NPZ_FILE)["vel_mag"], what="velocity magnitude")
+    data = dict(arrs, vel_mag=mag)
+    for k in S.STATS:
+        s = getattr(d, k + "_stats")
+        got, r = raw(s), rec["stats"][k]
+        want = np.array([rec_bits(r, "min"), rec_bits(r, "max")], dtype=np.uint64)
+        have = np.array([got["min"], got["max"]], dtype=np.uint64)
+        print(f"{case['name']} {k}: min {got['min']:016x} max {got['max']:016x} "
+              f"(record {r['min']} {r['max']}) sum {s.sum_val!r}")
+        assert_bits_equal(have.view(np.float64), want.view(np.float64),
+                          what=f"{case['name']} {k} (min, max)")
+        first = data[k].reshape(-1)[0]
+        if k != "vel_mag":
+            # a NaN in cell 0 included: the cell's own 64 bits
+            assert have.tolist() == want.tolist(), (case["name"], k)
+        elif np.isnan(first):
+            # the magnitude's NaN is computed: the bits of the device's own cell 0
+            assert have.tolist() == [int(S.bits(first).reshape(-1)[0])] * 2, (case["name"], k)
+        S.check_sum(s.sum_val, s.avg_val, data[k], f"{case['name']} {k}")
+    for k in S.FIELDS:
+        one, fused = raw(ctx.field_statistics(FID[k])), raw(getattr(d, k + "_stats"))
+        assert (one["min"], one["max"]) == (fused["min"], fused["max"]), k
+        assert same_sum(one["sum"], fused["sum"]) and same_sum(one["avg"], fused["avg"]), k
+    d0 = ctx.derived_statistics(False, S.RHO0)
+    assert stats_tuple(d0.vel_mag_stats) == (0.0, 0.0, 0.0, 0.0)
+    for k in S.FIELDS:
+        a, b = raw(getattr(d0, k + "_stats")), raw(getattr(d, k + "_stats"))
+        assert (a["min"], a["max"]) == (b["min"], b["max"]), k
+        assert same_sum(a["sum"], b["sum"]) and same_sum(a["avg"], b["avg"]), k
+
+
+def test_special_cases_are_deterministic(special_ctx):
+    """The same case twice, and again after an unrelated case on the context."""
+    case = S.BY_NAME["s96_zeros_nonneg_round"]
+
+    def run():
+        ctx, _ = special_ctx(case)
+        return bytes(ctx.derived_statistics(True, S.RHO0)), ctx.velocity_magnitude(), \
+            [bytes(ctx.field_statistics(FID[k])) for k in S.FIELDS]
+
+    first = run()
+    ctx, _ = special_ctx(case)
+    assert bytes(ctx.derived_statistics(True, S.RHO0)) == first[0]
+    for other in ("s96_nan_all", "s96_mag_extreme"):
+        ctx, _ = special_ctx(S.BY_NAME[other])
+        ctx.derived_statistics(True, S.RHO0)
+        ctx.velocity_magnitude()
+    again = run()
+    assert again[0] == first[0] and again[2] == first[2]
+    assert_bits_equal(again[1], first[1], what="velocity magnitude after an unrelated case")
+    # a case with NaNs: the same bits too, NaN payloads included
+    nan_case = S.BY_NAME["s96_nan_first_pos"]
+    ctx, _ = special_ctx(nan_case)
+    a = bytes(ctx.derived_statistics(True, S.RHO0))
+    special_ctx(case)
+    ctx, _ = special_ctx(nan_case)
+    assert bytes(ctx.derived_statistics(True, S.RHO0)) == a
+
+
+def csv_equal_up_to_nan_sign_of_averages(got: bytes, want: bytes, what: str):
+    """Byte for byte; failing that, the only difference allowed is the sign of
+    a NaN in an avg_ / sum_ column (a propagated NaN's sign is not part of the
+    contract), which is printed."""
+    if got == want:
+        return
+    g, w = got.decode().splitlines(), want.decode().splitlines()
+    assert len(g) == len(w) and g[0] == w[0], what
+    head = g[0].split(",")
+    for n, (gl, wl) in enumerate(zip(g[1:], w[1:]), start=1):
+        gc, wc = gl.split(","), wl.split(",")
+        assert len(gc) == len(wc) == len(head), (what, n)
+        for name, x, y in zip(head, gc, wc):
+            if x == y:
+                continue
+            assert name.startswith(("avg_", "sum_")) and {x, y} == {"nan", "-nan"}, \
+                (what, n, name, x, y)
+            print(f"{what}: row {n} column {name}: {x} for the record's {y}")
+
+
+@pytest.mark.parametrize("name", list(S.CSV_CASES))
+@pytest.mark.parametrize("mag", [0, 1])
+def test_special_csv_files_match_byte_for_byte(special_record, special_ctx, tmp_path, name, mag):
+    steps = S.CSV_CASES[name]
+    want = special_record["csv"][name]
+    nx, ny, nz = steps[0]["shape"]
+    g = api.Grid(nx, ny, nz, **K.grid_extent(steps[0]))
+    ts, st = tmp_path / "ts.csv", tmp_path / "st.csv"
+    for step, case in enumerate(steps):
+        ctx, _ = special_ctx(case, step)
+        t, dt, its, res, ms = K.csv_step_args(step)
+        prm = A.SolverParams()
+        prm.dt = dt
+        stats = A.SolverStats()
+        stats.iterations, stats.residual, stats.elapsed_time_ms = its, res, ms
+        assert ctx.write_csv_timeseries(str(ts), step, t, prm, stats, bool(mag),
+                                        step == 0) == A.CFD_SUCCESS
+        assert ctx.write_csv_statistics(str(st), step, t, S.RHO0, bool(mag),
+                                        step == 0) == A.CFD_SUCCESS
+        if step == 0:
+            for tag, direction in (("h", A.PROFILE_HORIZONTAL), ("v", A.PROFILE_VERTICAL)):
+                cl = tmp_path / f"cl{tag}.csv"
+                assert ctx.write_csv_centerline(str(cl), g, direction, S.RHO0,
+                                                bool(mag)) == A.CFD_SUCCESS
+                assert cl.read_bytes() == want[f"centerline_{tag}_mag{mag}"].encode(), tag
+    csv_equal_up_to_nan_sign_of_averages(ts.read_bytes(), want[f"timeseries_mag{mag}"].encode(),
+                                         f"{name} timeseries")
+    csv_equal_up_to_nan_sign_of_averages(st.read_bytes(), want[f"statistics_mag{mag}"].encode(),
+                                         f"{name} statistics")
