@@ -8,7 +8,7 @@ cfd_amd._native refuses a library whose id differs from the sources beside it.
 the device code inside a built library: PMC profiles are keyed on both
 (their byte counts depend on the kernels, not on host code). A header that
 defines kernels (kernels.hpp, relax_kernels.hpp, rk_kernels.hpp, ccf.hpp,
-rb2.hpp, bicgstab.hpp, dst_solve.hpp) is compiled by one translation unit, so
+rb2.hpp, bicgstab.hpp, transform_solve.hpp) is compiled by one translation unit, so
 the library holds one code object per unit and every device function once
 (tests/test_device_symbols.py). The HIP sources
 also hold host code, so a host-only edit changes the first key. It leaves the

@@ -30,21 +30,16 @@ struct Rb2Dec;    // rb2.hpp
 struct BcgState;  // bicgstab.hpp
 }  // namespace cfdhip
 
-// Device tables of the sine-transform solver for one axis length n
-// (dst_solve.hpp): the zero-padded sine matrix (pitch np) and e_n
-struct DstTable {
-    int n, np;
-    double* S;
-    double* e;
-};
-
-// ... of the cosine-transform solver (dct_solve.hpp): Q_n for the inverse
-// pass, its transpose for the forward pass (the passes apply the transpose of
-// the table they are given), and the Neumann e_n
-struct DctTable {
-    int n, np;
-    double* Q;
-    double* Qt;
+// Device tables of the direct transform solvers (transform_solve.hpp) for one
+// kind and axis length n: the zero-padded matrices (pitch np) of the forward
+// and the inverse pass, and e_n. Sine: the symmetric S_n, fwd == inv being one
+// allocation. Cosine: Q_n for the inverse pass and its transpose for the
+// forward pass (a pass applies the transpose of the table it is given).
+enum TransformKind { TR_SINE, TR_COSINE };
+struct TransformTable {
+    int kind, n, np;
+    double* fwd;
+    double* inv;
     double* e;
 };
 
@@ -155,13 +150,11 @@ struct hip_proj_ctx : TilePlan {
     double *rhat = nullptr, *bs = nullptr, *bt = nullptr;
     BcgState* bcgst = nullptr;
     double* bcg_part = nullptr;
-    // sine-transform solver (dst_solve.hpp): the tables, cached per distinct
-    // axis length by the first such solve, and the events around a solve
-    std::vector<DstTable> dst_tabs;
-    hipEvent_t dst_ev[2] = {nullptr, nullptr};
-    // cosine-transform solver (dct_solve.hpp): its tables, cached the same
-    // way; it shares the events
-    std::vector<DctTable> dct_tabs;
+    // direct transform solvers (transform_solve.hpp): the tables, cached per
+    // distinct (kind, axis length) by the first solve that needs them, and
+    // the events around a solve
+    std::vector<TransformTable> tr_tabs;
+    hipEvent_t tr_ev[2] = {nullptr, nullptr};
     // monitoring (derived_stats.hip), allocated by the first such call: the
     // statistics pass's workgroup records, totals and ticket; the velocity
     // magnitude in the padded layout
@@ -218,6 +211,20 @@ static cfd_status_t dalloc(hip_proj_ctx* c, double** ptr, size_t n) {
 }
 
 static size_t field_elems(const hip_proj_ctx* c) { return (size_t)c->ps * c->nz; }
+
+// A whole field between a caller's dense host array (rows of nx) and the
+// padded device layout (rows of pitch px), queued on the context's stream
+static hipError_t copy_in(hip_proj_ctx* c, double* dev, const double* host) {
+    return hipMemcpy2DAsync(dev, c->px * sizeof(double), host, c->nx * sizeof(double),
+                            c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
+                            c->stream);
+}
+
+static hipError_t copy_out(hip_proj_ctx* c, double* host, const double* dev) {
+    return hipMemcpy2DAsync(host, c->nx * sizeof(double), dev, c->px * sizeof(double),
+                            c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
+                            c->stream);
+}
 
 static double* field_ptr(hip_proj_ctx* c, int id) {
     switch (id) {

@@ -412,9 +412,7 @@ cfd_status_t hip_proj_velocity_magnitude(hip_proj_ctx_t* c, double* host) {
     a.mag = c->vmag;
     double tot[DS_NOUT];
     ST_TRY(ds_run(c, a, true, tot));
-    HIP_TRY(hipMemcpy2DAsync(host, c->nx * sizeof(double), c->vmag, c->px * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
-                             c->stream));
+    HIP_TRY(copy_out(c, host, c->vmag));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CFD_SUCCESS;
 }

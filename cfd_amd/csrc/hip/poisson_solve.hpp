@@ -1,9 +1,9 @@
 // poisson_solve.hpp -- the pressure solvers of the device context that are
 // compiled with projection_hip.hip (CG in its textbook and single-reduction
-// forms, BiCGSTAB, and through dst_solve.hpp / dct_solve.hpp the direct sine-
-// and cosine-transform solves) with their launch wrappers. The relaxation methods are a unit of their own,
-// relax_solve.hip; the polled device loop all share is poll.hpp. Host code
-// only; private to projection_hip.hip.
+// forms, BiCGSTAB, and through transform_solve.hpp the direct sine- and
+// cosine-transform solves) with their launch wrappers. The relaxation methods
+// are a unit of their own, relax_solve.hip; the polled device loop all share
+// is poll.hpp. Host code only; private to projection_hip.hip.
 #pragma once
 
 #include "poll.hpp"
@@ -469,7 +469,6 @@ static cfd_status_t bicgstab_solve(hip_proj_ctx* c, double dx, double dy, double
     return finish_stats(c, s, s.res);
 }
 
-// the direct sine-transform solver: uses ensure_aux and the poll helpers
-#include "dst_solve.hpp"
-// the direct cosine-transform solver: the same passes with cosine tables
-#include "dct_solve.hpp"
+// the direct sine- and cosine-transform solvers: use ensure_aux and the poll
+// helpers
+#include "transform_solve.hpp"

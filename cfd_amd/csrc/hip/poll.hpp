@@ -1,6 +1,6 @@
 // poll.hpp -- the polled device loop the iterative pressure solvers share
-// (poisson_solve.hpp: CG, BiCGSTAB; relax_solve.hip; dst_solve.hpp reads a
-// final state through it). Host templates only.
+// (poisson_solve.hpp: CG, BiCGSTAB; relax_solve.hip; transform_solve.hpp reads
+// a final state through it). Host templates only.
 #pragma once
 
 #include "ctx.hpp"

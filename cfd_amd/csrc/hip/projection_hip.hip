@@ -145,16 +145,12 @@ static void free_ctx(hip_proj_ctx* c) {
     if (c->rb2dec) hipFree(c->rb2dec);
     if (c->bcgst) hipFree(c->bcgst);
     if (c->bcg_part) hipFree(c->bcg_part);
-    for (const DstTable& t : c->dst_tabs) {
-        if (t.S) hipFree(t.S);
+    for (const TransformTable& t : c->tr_tabs) {
+        if (t.fwd) hipFree(t.fwd);
+        if (t.inv && t.inv != t.fwd) hipFree(t.inv);
         if (t.e) hipFree(t.e);
     }
-    for (const DctTable& t : c->dct_tabs) {
-        if (t.Q) hipFree(t.Q);
-        if (t.Qt) hipFree(t.Qt);
-        if (t.e) hipFree(t.e);
-    }
-    for (hipEvent_t e : c->dst_ev)
+    for (hipEvent_t e : c->tr_ev)
         if (e) hipEventDestroy(e);
     if (c->partials) hipFree(c->partials);
     if (c->counter) hipFree(c->counter);
@@ -515,9 +511,7 @@ cfd_status_t hip_proj_set_field(hip_proj_ctx_t* c, int id, const double* host) {
     if (!d) return CFD_ERROR_INVALID;
     c->resident = 0;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(d, c->px * sizeof(double), host, c->nx * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                             c->stream));
+    HIP_TRY(copy_in(c, d, host));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (id == HIP_FIELD_T) c->have_T = c->T_dirty = 1;
     return CFD_SUCCESS;
@@ -529,9 +523,7 @@ cfd_status_t hip_proj_get_field(hip_proj_ctx_t* c, int id, double* host) {
     double* d = field_ptr(c, id);
     if (!d) return CFD_ERROR_INVALID;
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpy2DAsync(host, c->nx * sizeof(double), d, c->px * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
-                             c->stream));
+    HIP_TRY(copy_out(c, host, d));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CFD_SUCCESS;
 }
@@ -800,15 +792,12 @@ void ctx_queue_max_T(hip_proj_ctx* c) {
 // The sine- and cosine-transform solves work on whole z lines: a Z-slab
 // context is refused before anything is uploaded or launched (as BiCGSTAB's
 // refusals).
-static cfd_status_t dst_refuse_slab(const hip_proj_ctx* c, int method) {
-    if (method == HIP_POISSON_DCT && dist(c)) {
-        set_err(CFD_ERROR_UNSUPPORTED,
-                "projection_hip: the DCT pressure solve runs on one device, not on Z-slabs");
-        return CFD_ERROR_UNSUPPORTED;
-    }
-    if (method != HIP_POISSON_DST || !dist(c)) return CFD_SUCCESS;
+static cfd_status_t transform_refuse_slab(const hip_proj_ctx* c, int method) {
+    if (transform_kind(method) < 0 || !dist(c)) return CFD_SUCCESS;
     set_err(CFD_ERROR_UNSUPPORTED,
-            "projection_hip: the DST pressure solve runs on one device, not on Z-slabs");
+            method == HIP_POISSON_DST
+                ? "projection_hip: the DST pressure solve runs on one device, not on Z-slabs"
+                : "projection_hip: the DCT pressure solve runs on one device, not on Z-slabs");
     return CFD_ERROR_UNSUPPORTED;
 }
 
@@ -820,7 +809,7 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
     if (!c) return CFD_ERROR_INVALID;
     cfd_status_t s = ctx_validate_params(c, g, prm);
     if (s != CFD_SUCCESS) return s;
-    ST_TRY(dst_refuse_slab(c, c->cfg.poisson_method));
+    ST_TRY(transform_refuse_slab(c, c->cfg.poisson_method));
     HIP_TRY(hipSetDevice(c->device));
     const size_t nz = c->nzg;
     const double dx = g->dx[0], dy = g->dy[0];
@@ -909,12 +898,9 @@ static cfd_status_t step_device_impl(hip_proj_ctx_t* c, const grid* g,
         if (method == HIP_POISSON_JACOBI)
             HIP_TRY(hipMemsetAsync(c->xt, 0, field_elems(c) * sizeof(double), c->stream));
         int maxit = c->cfg.poisson_max_iter;
-        if (method == HIP_POISSON_DST)
-            ps = dst_solve(c, dx, dy, dz, c->cfg.poisson_tolerance,
-                           c->cfg.poisson_abs_tolerance);
-        else if (method == HIP_POISSON_DCT)
-            ps = dct_solve(c, dx, dy, dz, c->cfg.poisson_tolerance,
-                           c->cfg.poisson_abs_tolerance);
+        if (transform_kind(method) >= 0)
+            ps = transform_solve(c, transform_kind(method), dx, dy, dz,
+                                 c->cfg.poisson_tolerance, c->cfg.poisson_abs_tolerance);
         else
             ps = relax_solve(c, method, dx, dy, dz, c->cfg.poisson_tolerance,
                              c->cfg.poisson_abs_tolerance, maxit,
@@ -1017,7 +1003,7 @@ static cfd_status_t host_steps(hip_proj_ctx_t* c, flow_field* f, const grid* g,
     if (f->nx < 3 || f->ny < 3 || (f->nz > 1 && f->nz < 3)) return CFD_ERROR_INVALID;
     cfd_status_t s = ctx_validate_params(c, g, prm);
     if (s != CFD_SUCCESS) return s;
-    ST_TRY(dst_refuse_slab(c, c->cfg.poisson_method));
+    ST_TRY(transform_refuse_slab(c, c->cfg.poisson_method));
     if (n_steps <= 0) return CFD_SUCCESS;
     const bool need_T = (prm->beta != 0.0) || (prm->alpha > 0.0);
     const bool shell = shell_ok && c->cfg.dirty_faces > 0 && ctx_shell_fits(c, 2);
@@ -1217,7 +1203,7 @@ cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* c, int method, double* x,
             return CFD_ERROR_UNSUPPORTED;
         }
     }
-    ST_TRY(dst_refuse_slab(c, method));
+    ST_TRY(transform_refuse_slab(c, method));
     if (method == HIP_POISSON_DCT && bc_mode != HIP_POISSON_BC_NEUMANN) {
         // the cosine transform diagonalises the Neumann problem only
         set_err(CFD_ERROR_UNSUPPORTED,
@@ -1227,9 +1213,7 @@ cfd_status_t hip_proj_poisson_solve_ex(hip_proj_ctx_t* c, int method, double* x,
     HIP_TRY(hipSetDevice(c->device));
     if (bc_mode == HIP_POISSON_BC_FIXED) {
         if (!c->bcfix) ST_TRY(dalloc(c, &c->bcfix, field_elems(c)));
-        HIP_TRY(hipMemcpy2DAsync(c->bcfix, c->px * sizeof(double), bc_values,
-                                 c->nx * sizeof(double), c->nx * sizeof(double), c->ny * c->nz,
-                                 hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(copy_in(c, c->bcfix, bc_values));
     }
     c->poisson_bc = bc_mode;
     const cfd_status_t s = poisson_solve_impl(c, method, x, rhs, dx, dy, dz, params, stats);
@@ -1256,12 +1240,8 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
     }
     cfd_status_t s = ensure_aux(c, true, method == HIP_POISSON_JACOBI);
     if (s != CFD_SUCCESS) return s;
-    HIP_TRY(hipMemcpy2DAsync(c->rhs, c->px * sizeof(double), rhs, c->nx * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                             c->stream));
-    HIP_TRY(hipMemcpy2DAsync(c->pn, c->px * sizeof(double), x, c->nx * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                             c->stream));
+    HIP_TRY(copy_in(c, c->rhs, rhs));
+    HIP_TRY(copy_in(c, c->pn, x));
     if (method == HIP_POISSON_JACOBI)
         HIP_TRY(hipMemcpyAsync(c->xt, c->pn, field_elems(c) * sizeof(double),
                                hipMemcpyDeviceToDevice, c->stream));
@@ -1270,87 +1250,59 @@ static cfd_status_t poisson_solve_impl(hip_proj_ctx_t* c, int method, double* x,
         s = cg_solve(c, dx, dy, dz, dc, RHS_FROM_ARRAY, rel, abs_tol, maxit, ci, true);
     } else if (method == HIP_POISSON_BICGSTAB) {
         s = bicgstab_solve(c, dx, dy, dz, rel, abs_tol, maxit, ci);
-    } else if (method == HIP_POISSON_DST) {
-        s = dst_solve(c, dx, dy, dz, rel, abs_tol);
-    } else if (method == HIP_POISSON_DCT) {
-        s = dct_solve(c, dx, dy, dz, rel, abs_tol);
+    } else if (transform_kind(method) >= 0) {
+        s = transform_solve(c, transform_kind(method), dx, dy, dz, rel, abs_tol);
     } else {
         s = relax_solve(c, method, dx, dy, dz, rel, abs_tol, maxit, ci, omega);
     }
-    HIP_TRY(hipMemcpy2DAsync(x, c->nx * sizeof(double), c->pn, c->px * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
-                             c->stream));
+    HIP_TRY(copy_out(c, x, c->pn));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (stats) {
         *stats = c->pstats;
         // the direct solves report their device time (events around the solve)
-        if (method != HIP_POISSON_DST && method != HIP_POISSON_DCT) stats->elapsed_time_ms = 0.0;
+        if (transform_kind(method) < 0) stats->elapsed_time_ms = 0.0;
     }
     return s;
 }
 
-cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* c, double* field_host, int axis) {
+// One transform pass of `method` on its own; fn: the entry point's name
+static cfd_status_t transform_impl(hip_proj_ctx_t* c, int method, const char* fn,
+                                   double* field_host, int axis, bool inverse) {
     GroupHostLock hl_(c);
     if (!c || !field_host) return CFD_ERROR_INVALID;
-    if (axis < 0 || axis > 2) {
-        set_err(CFD_ERROR_INVALID, "hip_proj_dst_transform: axis must be 0 (x), 1 (y) or 2 (z)");
+    const char* why = nullptr;
+    if (axis < 0 || axis > 2) why = "axis must be 0 (x), 1 (y) or 2 (z)";
+    else if (axis == 2 && c->nz == 1) why = "a 2-D context has no z axis";
+    if (why) {
+        char msg[96];
+        snprintf(msg, sizeof(msg), "%s: %s", fn, why);
+        set_err(CFD_ERROR_INVALID, msg);
         return CFD_ERROR_INVALID;
     }
-    if (axis == 2 && c->nz == 1) {
-        set_err(CFD_ERROR_INVALID, "hip_proj_dst_transform: a 2-D context has no z axis");
-        return CFD_ERROR_INVALID;
-    }
-    ST_TRY(dst_refuse_slab(c, HIP_POISSON_DST));
+    ST_TRY(transform_refuse_slab(c, method));
     c->resident = 0;  // the transform runs in the step's pressure buffers
     HIP_TRY(hipSetDevice(c->device));
     ST_TRY(ensure_aux(c, false, true));
-    DstTabs T;
-    ST_TRY(dst_tables_of(c, &T));
+    TransformTabs T;
+    ST_TRY(tables_of(c, transform_kind(method), &T));
     // the input goes to both fields: the pass reads the interior of one and
     // writes the interior of the other, whose boundary is the caller's
-    for (double* d : {c->pn, c->xt})
-        HIP_TRY(hipMemcpy2DAsync(d, c->px * sizeof(double), field_host, c->nx * sizeof(double),
-                                 c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                                 c->stream));
-    dst_pass(c, T, axis, c->pn, c->xt);
+    for (double* d : {c->pn, c->xt}) HIP_TRY(copy_in(c, d, field_host));
+    transform_pass(c, T, axis, inverse, c->pn, c->xt);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy2DAsync(field_host, c->nx * sizeof(double), c->xt, c->px * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
-                             c->stream));
+    HIP_TRY(copy_out(c, field_host, c->xt));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CFD_SUCCESS;
 }
 
+cfd_status_t hip_proj_dst_transform(hip_proj_ctx_t* c, double* field_host, int axis) {
+    return transform_impl(c, HIP_POISSON_DST, "hip_proj_dst_transform", field_host, axis, false);
+}
+
 cfd_status_t hip_proj_dct_transform(hip_proj_ctx_t* c, double* field_host, int axis,
                                     int inverse) {
-    GroupHostLock hl_(c);
-    if (!c || !field_host) return CFD_ERROR_INVALID;
-    if (axis < 0 || axis > 2) {
-        set_err(CFD_ERROR_INVALID, "hip_proj_dct_transform: axis must be 0 (x), 1 (y) or 2 (z)");
-        return CFD_ERROR_INVALID;
-    }
-    if (axis == 2 && c->nz == 1) {
-        set_err(CFD_ERROR_INVALID, "hip_proj_dct_transform: a 2-D context has no z axis");
-        return CFD_ERROR_INVALID;
-    }
-    ST_TRY(dst_refuse_slab(c, HIP_POISSON_DCT));
-    c->resident = 0;  // the transform runs in the step's pressure buffers
-    HIP_TRY(hipSetDevice(c->device));
-    ST_TRY(ensure_aux(c, false, true));
-    DctTabs T;
-    ST_TRY(dct_tables_of(c, &T));
-    // as hip_proj_dst_transform: the input goes to both fields
-    for (double* d : {c->pn, c->xt})
-        HIP_TRY(hipMemcpy2DAsync(d, c->px * sizeof(double), field_host, c->nx * sizeof(double),
-                                 c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                                 c->stream));
-    dct_pass(c, T, axis, inverse != 0, c->pn, c->xt);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy2DAsync(field_host, c->nx * sizeof(double), c->xt, c->px * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CFD_SUCCESS;
+    return transform_impl(c, HIP_POISSON_DCT, "hip_proj_dct_transform", field_host, axis,
+                          inverse != 0);
 }
 
 double hip_proj_cg_fixed_iters(hip_proj_ctx_t* c, const double* rhs_host, double dx, double dy,
@@ -1367,10 +1319,7 @@ double hip_proj_cg_fixed_iters_ex(hip_proj_ctx_t* c, const double* rhs_host, dou
     if (!rhs_host && (!c->us || !c->vs || !c->ws)) return -1.0;
     if (rhs_host) {
         if (ensure_aux(c, true, false) != CFD_SUCCESS) return -1.0;
-        if (hipMemcpy2DAsync(c->rhs, c->px * sizeof(double), rhs_host, c->nx * sizeof(double),
-                             c->nx * sizeof(double), c->ny * c->nz, hipMemcpyHostToDevice,
-                             c->stream) != hipSuccess)
-            return -1.0;
+        if (copy_in(c, c->rhs, rhs_host) != hipSuccess) return -1.0;
     }
     hipMemsetAsync(c->pn, 0, field_elems(c) * sizeof(double), c->stream);
     hipEvent_t a, b;

@@ -1,8 +1,11 @@
-// dst_solve.hpp -- the direct sine-transform pressure solver (HIP_POISSON_DST).
+// transform_solve.hpp -- the direct transform pressure solvers: sine
+// (HIP_POISSON_DST) and cosine (HIP_POISSON_DCT). One table cache, one pass
+// function and one solve serve both; what differs by kind is the table, the
+// residual that decides the status, the boundary write and the scaling.
 //
-// Inside a solve the boundary cells of x are frozen (the reference's CG
-// applies its BC to x only before and after the loop), so the interior system
-// is the constant-coefficient 7-point Laplacian with Dirichlet data. On the
+// The sine solve. Inside a solve the boundary cells of x are frozen (the
+// reference's CG applies its BC to x only before and after the loop), so the
+// interior system is the constant-coefficient 7-point Laplacian with Dirichlet data. On the
 // uniform box the type-I sine transform along each axis diagonalises it:
 //   x = S_x S_y S_z [ norm / (lx[i] + ly[j] + lz[k]) * S_z S_y S_x b ],
 //   b = -rhs + (frozen boundary neighbours) / h^2,  norm = prod 2 / (n + 1).
@@ -21,6 +24,31 @@
 // cell): out-of-range rows, columns and k steps are masked to zero on the
 // load and skipped on the store; the table is zero-padded to its 64-row tile.
 // The summation order is fixed, so a solve is bitwise reproducible.
+//
+// The cosine solve. Red-Black SOR and Jacobi apply the Neumann boundary
+// condition after every sweep, so at their fixed point every shell cell equals
+// its interior neighbour and the interior operator is the cell-centred Neumann
+// Laplacian: the 7-point stencil whose end cells lose the missing neighbour's
+// term. On the uniform box the orthonormal type-II cosine transform along each
+// axis diagonalises it,
+//   Q_n[a][b] = w_a cos(pi a (2 b + 1) / (2 n)),  lambda_n[a] = 4 sin^2(pi a / (2 n)) / h^2,
+//   x = Qx^T Qy^T Qz^T [ (Qz Qy Qx (-rhs)) / (lx[i] + ly[j] + lz[k]) ]   (interior),
+// followed by the Neumann shell (the sign is the relaxation solvers': they
+// solve lap(x) = rhs, and the operator above is -lap). The transforms are the
+// sine solver's passes with cosine tables. A pass computes out[a] = sum_b
+// T[b][a] in[b]; the sine table is symmetric, Q is not: the forward pass is
+// given Q^T, the inverse pass Q.
+//
+// The zero mode. lambda(0, 0, 0) = 0: the operator is singular, its null
+// space the constants. The coefficient of that mode is set to exactly 0.0 and
+// never divided, so the interior mean of the result is zero to rounding. A
+// right-hand side whose interior mean m is not zero has no solution; the
+// result is then the least-squares one, whose residual is m in every cell
+// (L-inf residual |m|), which is also where the iterations' residual ends up:
+// the status is the one they would reach. The pressure constant differs from
+// RB-SOR's or Jacobi's in every case (they keep what their start and their
+// splitting leave); only grad p enters the projection step.
+//
 // Host code + kernels; private to projection_hip.hip (through
 // poisson_solve.hpp).
 #pragma once
@@ -67,7 +95,7 @@ constexpr int DST_XP = 66;   // LDS row pitch: conflict-free fragment reads
 
 // Workgroup = 4 waves on one 64-row tile of the output and 4 adjacent
 // 16-column tiles (the waves share the table loads through the L1). COS (with
-// SCALE): the cosine solve's scaling (dct_solve.hpp), a plain division by the
+// SCALE): the cosine solve's scaling, a plain division by the
 // eigenvalue sum with the zero mode written as 0.0 and never divided.
 template <bool SCALE, bool COS = false>
 static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
@@ -126,7 +154,7 @@ static __global__ __launch_bounds__(256) void k_dst_strided(DstAxis g,
 // Workgroup = 4 waves on 32 lines (consecutive j of one plane) x 256 output
 // columns, 64 per wave. FORM_B: the input is b = -rhs + (frozen boundary
 // neighbours of xb) / h^2, formed on the load (in = rhs). NEG (without
-// FORM_B): the input is -in, with no boundary terms (dct_solve.hpp).
+// FORM_B): the input is -in, with no boundary terms (the cosine solve).
 template <bool FORM_B, bool NEG = false>
 static __global__ __launch_bounds__(256) void k_dst_x(DstRows g, const double* __restrict__ S,
                                                       const double* __restrict__ in,
@@ -211,50 +239,66 @@ static __global__ __launch_bounds__(256) void k_dst_x(DstRows g, const double* _
 
 }  // namespace cfdhip
 
-// The cached tables of one axis length (device copies)
-static cfd_status_t dst_table(hip_proj_ctx* c, int n, const DstTable** out) {
-    for (const DstTable& t : c->dst_tabs)
-        if (t.n == n) {
+// the kind of a direct transform method (hip_poisson_method_t), -1 for any other
+static int transform_kind(int method) {
+    return method == HIP_POISSON_DST ? TR_SINE : method == HIP_POISSON_DCT ? TR_COSINE : -1;
+}
+
+// The cached device tables of one kind and axis length. The entry is pushed
+// with n = -1, which no lookup matches, so the context owns its allocations
+// from the start (free_ctx) and a failed allocation or copy leaves nothing
+// that a later solve could find; n is set once the entry is complete.
+static cfd_status_t transform_table(hip_proj_ctx* c, int kind, int n,
+                                    const TransformTable** out) {
+    for (const TransformTable& t : c->tr_tabs)
+        if (t.kind == kind && t.n == n) {
             *out = &t;
             return CFD_SUCCESS;
         }
-    const size_t np = dst_table_pitch((size_t)n);
-    std::vector<double> hs(np * np), he((size_t)n);
-    dst_fill_sine_table((size_t)n, hs.data());
-    dst_fill_eigenvalues((size_t)n, he.data());
-    DstTable t{n, (int)np, nullptr, nullptr};
-    HIP_TRY(hipMalloc((void**)&t.S, hs.size() * sizeof(double)));
-    c->dst_tabs.push_back(t);  // owned by the context from here (free_ctx)
-    HIP_TRY(hipMalloc((void**)&c->dst_tabs.back().e, he.size() * sizeof(double)));
+    const bool cosine = (kind == TR_COSINE);
+    const size_t np = dst_table_pitch((size_t)n), bytes = np * np * sizeof(double);
+    std::vector<double> hf(np * np), hi(cosine ? np * np : 0), he((size_t)n);
+    if (cosine) {
+        dct_fill_cos_tables((size_t)n, hi.data(), hf.data());
+        dct_fill_eigenvalues((size_t)n, he.data());
+    } else {
+        dst_fill_sine_table((size_t)n, hf.data());
+        dst_fill_eigenvalues((size_t)n, he.data());
+    }
+    c->tr_tabs.push_back(TransformTable{kind, -1, (int)np, nullptr, nullptr, nullptr});
+    TransformTable& t = c->tr_tabs.back();
+    HIP_TRY(hipMalloc((void**)&t.fwd, bytes));
+    if (cosine) HIP_TRY(hipMalloc((void**)&t.inv, bytes));
+    else t.inv = t.fwd;  // S is symmetric: one allocation
+    HIP_TRY(hipMalloc((void**)&t.e, he.size() * sizeof(double)));
     // pageable sources: synchronous copies (ordered before later stream work)
-    HIP_TRY(hipMemcpy(c->dst_tabs.back().S, hs.data(), hs.size() * sizeof(double),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->dst_tabs.back().e, he.data(), he.size() * sizeof(double),
-                      hipMemcpyHostToDevice));
-    *out = &c->dst_tabs.back();
+    HIP_TRY(hipMemcpy(t.fwd, hf.data(), bytes, hipMemcpyHostToDevice));
+    if (cosine) HIP_TRY(hipMemcpy(t.inv, hi.data(), bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t.e, he.data(), he.size() * sizeof(double), hipMemcpyHostToDevice));
+    t.n = n;
+    *out = &t;
     return CFD_SUCCESS;
 }
 
-// the tables of the context's axes (tz == nullptr in 2-D); the vector may
-// grow while they are looked up, so the pointers are taken afterwards
-struct DstTabs {
-    const DstTable *tx, *ty, *tz;
+// the tables of the context's axes x, y, z (z: nullptr in 2-D)
+struct TransformTabs {
+    const TransformTable* t[3];
 };
 
-static cfd_status_t dst_tables_of(hip_proj_ctx* c, DstTabs* T) {
-    const DstTable* t = nullptr;
+// two rounds: the vector may grow while the tables are built in the first,
+// so the pointers are those of the second
+static cfd_status_t tables_of(hip_proj_ctx* c, int kind, TransformTabs* T) {
     const int n[3] = {(int)c->nx - 2, (int)c->ny - 2, c->nz > 1 ? (int)c->nz - 2 : 0};
-    for (int a = 0; a < 3; ++a)
-        if (n[a] > 0) ST_TRY(dst_table(c, n[a], &t));
-    ST_TRY(dst_table(c, n[0], &T->tx));
-    ST_TRY(dst_table(c, n[1], &T->ty));
-    T->tz = nullptr;
-    if (n[2] > 0) ST_TRY(dst_table(c, n[2], &T->tz));
+    for (int round = 0; round < 2; ++round)
+        for (int a = 0; a < 3; ++a) {
+            T->t[a] = nullptr;
+            if (n[a] > 0) ST_TRY(transform_table(c, kind, n[a], &T->t[a]));
+        }
     return CFD_SUCCESS;
 }
 
 // The launch geometry of the x pass (table pitch np) and of a strided pass
-// along axis 1 (y) or 2 (z) with n points; shared with dct_solve.hpp
+// along axis 1 (y) or 2 (z) with n points
 static DstRows dst_rows_geo(const hip_proj_ctx* c, int np) {
     const bool is3d = c->nz > 1;
     DstRows g;
@@ -292,105 +336,140 @@ static DstAxis dst_axis_geo(const hip_proj_ctx* c, int axis, int n, int np) {
     return g;
 }
 
-// One unnormalised DST-I pass of the interior along `axis` (0 x, 1 y, 2 z):
-// in -> out (distinct fields). form_b (axis 0): the input is b formed from
-// in = rhs and the shell of xb. sc (axes 1, 2): the eigenvalue scaling on the
-// store.
-static void dst_pass(hip_proj_ctx* c, const DstTabs& T, int axis, const double* in, double* out,
-                     const DstScale* sc = nullptr, const double* xb = nullptr,
-                     const Lap* L = nullptr) {
-    const bool is3d = c->nz > 1;
+// One pass of the interior along `axis` (0 x, 1 y, 2 z): in -> out (distinct
+// fields). Sine: the unnormalised DST-I, its own inverse up to norm. Cosine:
+// the orthonormal DCT-II, or with `inverse` its transpose, the DCT-III. sc
+// (axes 1, 2): the eigenvalue scaling on the store, the kind's own. load (axis
+// 0): the input as PassLoad says; LOAD_FORM_B takes the shell from xb and L.
+enum PassLoad {
+    LOAD_PLAIN,   // in
+    LOAD_NEG,     // -in
+    LOAD_FORM_B,  // b formed from in = rhs and the frozen shell of xb
+};
+
+static void transform_pass(hip_proj_ctx* c, const TransformTabs& T, int axis, bool inverse,
+                           const double* in, double* out, const DstScale* sc = nullptr,
+                           PassLoad load = LOAD_PLAIN, const double* xb = nullptr,
+                           const Lap* L = nullptr) {
+    const TransformTable* t = T.t[axis];
+    const double* tab = inverse ? t->inv : t->fwd;
     if (axis == 0) {
-        const DstRows g = dst_rows_geo(c, T.tx->np);
+        const DstRows g = dst_rows_geo(c, t->np);
         const dim3 grid((unsigned)(g.tiles_a * g.tiles_j * g.nk));
-        if (xb)
-            klaunch(c, k_dst_x<true>, grid, dim3(256), g, T.tx->S, in, xb, out, *L, is3d ? 1 : 0);
+        if (load == LOAD_FORM_B)
+            klaunch(c, k_dst_x<true>, grid, dim3(256), g, tab, in, xb, out, *L,
+                    c->nz > 1 ? 1 : 0);
+        else if (load == LOAD_NEG)
+            klaunch(c, k_dst_x<false, true>, grid, dim3(256), g, tab, in, nullptr, out, Lap{}, 0);
         else
-            klaunch(c, k_dst_x<false>, grid, dim3(256), g, T.tx->S, in, nullptr, out, Lap{}, 0);
+            klaunch(c, k_dst_x<false>, grid, dim3(256), g, tab, in, nullptr, out, Lap{}, 0);
         return;
     }
-    const DstTable* t = (axis == 1) ? T.ty : T.tz;
     const DstAxis g = dst_axis_geo(c, axis, t->n, t->np);
     const dim3 grid((unsigned)(g.tiles_c * g.tiles_a * g.nb));
-    if (sc) klaunch(c, k_dst_strided<true>, grid, dim3(256), g, t->S, in, out, *sc);
-    else klaunch(c, k_dst_strided<false>, grid, dim3(256), g, t->S, in, out, DstScale{});
+    if (!sc)
+        klaunch(c, k_dst_strided<false>, grid, dim3(256), g, tab, in, out, DstScale{});
+    else if (t->kind == TR_COSINE)
+        klaunch(c, k_dst_strided<true, true>, grid, dim3(256), g, tab, in, out, *sc);
+    else
+        klaunch(c, k_dst_strided<true>, grid, dim3(256), g, tab, in, out, *sc);
 }
 
 // ---------------------------------------------------------------------------
 // The solve: x in c->pn, rhs in c->rhs. The transforms ping-pong between
-// c->xt and the interior of c->pn (whose values are not needed once b is
-// formed; its shell is never written), so rhs stays intact for the final
-// residual. r0 and both residual norms come from k_cg_setup (r = -rhs +
-// lap(x) on the interior, with x's boundary as it stands). max_iterations,
+// c->xt and the interior of c->pn (whose values are not needed once the first
+// pass has read its input; its shell is written by the boundary condition
+// only), so rhs stays intact for the final residual. max_iterations,
 // check_interval and omega play no part.
 // ---------------------------------------------------------------------------
-static cfd_status_t dst_solve(hip_proj_ctx* c, double dx, double dy, double dz, double rel_tol,
-                              double abs_tol) {
-    const bool is3d = c->nz > 1;
+static cfd_status_t transform_solve(hip_proj_ctx* c, int kind, double dx, double dy, double dz,
+                                    double rel_tol, double abs_tol) {
+    const bool is3d = c->nz > 1, sine = (kind == TR_SINE);
     const Lap L = make_lap(dx, dy, is3d ? dz : 0.0);
-    const int G = tile_grid(c);
     const DirVals dv{};
     double* x = c->pn;
     ST_TRY(ensure_aux(c, true, true));
-    DstTabs T;
-    ST_TRY(dst_tables_of(c, &T));
-    for (hipEvent_t& e : c->dst_ev)
+    TransformTabs T;
+    ST_TRY(tables_of(c, kind, &T));
+    for (hipEvent_t& e : c->tr_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c->dst_ev[0], c->stream));
-    // poisson_solver_apply_bc(x) at solve start, as cg_solve: the default
-    // Neumann shell, or the caller's boundary left as it is
+    HIP_TRY(hipEventRecord(c->tr_ev[0], c->stream));
+    // sine: poisson_solver_apply_bc(x) at solve start, as cg_solve: the
+    // default Neumann shell, or the caller's boundary left as it is. cosine
+    // (linear_solver.c:397-485): the residual of x as it stands
     const bool neumann = (c->poisson_bc == HIP_POISSON_BC_NEUMANN);
-    if (neumann) launch_bc(c, x, 0, dv);
-    auto residual = [&](CgState* s) -> cfd_status_t {
+    if (sine && neumann) launch_bc(c, x, 0, dv);
+    // the residual of x: sine, CG's || -rhs + lap(x) || from k_cg_setup with
+    // x's boundary as it stands; cosine, the relaxation solvers' L-inf
+    // residual (k_residual_linf). tol: the tolerance the residual sets
+    auto residual = [&](double* res, double* tol = nullptr) -> cfd_status_t {
+        if (!sine) {
+            ST_TRY(relax_residual_linf(c, x, dx, dy, is3d ? dz : 0.0, res));
+            if (tol) *tol = std::max(rel_tol * *res, abs_tol);
+            return CFD_SUCCESS;
+        }
         timed(c, HIP_KT_CG_SETUP, [&] {
-            klaunch(c, k_cg_setup<false, false, true, false>, dim3(G), dim3(NT), c->geo, L,
-                    DivCoef{}, nullptr, nullptr, nullptr, c->rhs, x, c->r, c->st, c->partials,
-                    c->counter, rel_tol, abs_tol, 1, 1, c->dsum, nullptr);
+            klaunch(c, k_cg_setup<false, false, true, false>, dim3(tile_grid(c)), dim3(NT),
+                    c->geo, L, DivCoef{}, nullptr, nullptr, nullptr, c->rhs, x, c->r, c->st,
+                    c->partials, c->counter, rel_tol, abs_tol, 1, 1, c->dsum, nullptr);
         });
-        return poll_final(c, c->st, s);
+        CgState s;
+        ST_TRY(poll_final(c, c->st, &s));
+        *res = s.res0;
+        if (tol) *tol = s.tol;
+        return CFD_SUCCESS;
     };
-    CgState s0;
-    ST_TRY(residual(&s0));
-    c->pstats.initial_residual = s0.res0;
-    if (s0.res0 < abs_tol) {  // linear_solver_cg.c:353-361: no end BC
+    double res0 = 0.0, tol = 0.0;
+    ST_TRY(residual(&res0, &tol));
+    c->pstats.initial_residual = res0;
+    if (res0 < abs_tol) {  // linear_solver_cg.c:353-361: no end BC
         flush_timing(c);
         c->pstats.status = POISSON_CONVERGED;
         c->pstats.iterations = 0;
-        c->pstats.final_residual = s0.res0;
+        c->pstats.final_residual = res0;
         c->pstats.elapsed_time_ms = 0.0;
         return CFD_SUCCESS;
     }
     DstScale sc{};
-    sc.norm = (2.0 / (double)(c->nx - 1)) * (2.0 / (double)(c->ny - 1));
-    if (is3d) sc.norm *= 2.0 / (double)(c->nz - 1);
-    sc.ec = T.tx->e;
-    sc.hc = L.dx2_inv;
-    dst_pass(c, T, 0, c->rhs, c->xt, nullptr, x, &L);
-    if (is3d) {
-        sc.ea = T.tz->e, sc.ha = L.inv_dz2;
-        sc.eb = T.ty->e, sc.hb = L.dy2_inv;
-        dst_pass(c, T, 1, c->xt, x);
-        dst_pass(c, T, 2, x, c->xt, &sc);
-        dst_pass(c, T, 2, c->xt, x);
-        dst_pass(c, T, 1, x, c->xt);
-    } else {
-        sc.ea = T.ty->e, sc.ha = L.dy2_inv;
-        sc.eb = nullptr, sc.hb = 0.0;
-        dst_pass(c, T, 1, c->xt, x, &sc);
-        dst_pass(c, T, 1, x, c->xt);
+    sc.norm = 1.0;  // Q is orthonormal
+    if (sine) {
+        sc.norm = (2.0 / (double)(c->nx - 1)) * (2.0 / (double)(c->ny - 1));
+        if (is3d) sc.norm *= 2.0 / (double)(c->nz - 1);
     }
-    dst_pass(c, T, 0, c->xt, x);
-    // || b - A x || with the boundary still frozen
-    CgState s1;
-    ST_TRY(residual(&s1));
-    if (neumann) launch_bc(c, x, 0, dv);  // linear_solver_cg.c:447
-    HIP_TRY(hipEventRecord(c->dst_ev[1], c->stream));
-    HIP_TRY(hipEventSynchronize(c->dst_ev[1]));
+    sc.ec = T.t[0]->e;
+    sc.hc = L.dx2_inv;
+    // the first pass forms b from rhs and the frozen shell of x (sine), or
+    // takes -rhs (cosine)
+    transform_pass(c, T, 0, false, c->rhs, c->xt, nullptr, sine ? LOAD_FORM_B : LOAD_NEG, x, &L);
+    if (is3d) {
+        sc.ea = T.t[2]->e, sc.ha = L.inv_dz2;
+        sc.eb = T.t[1]->e, sc.hb = L.dy2_inv;
+        transform_pass(c, T, 1, false, c->xt, x);
+        transform_pass(c, T, 2, false, x, c->xt, &sc);
+        transform_pass(c, T, 2, true, c->xt, x);
+        transform_pass(c, T, 1, true, x, c->xt);
+    } else {
+        sc.ea = T.t[1]->e, sc.ha = L.dy2_inv;
+        sc.eb = nullptr, sc.hb = 0.0;
+        transform_pass(c, T, 1, false, c->xt, x, &sc);
+        transform_pass(c, T, 1, true, x, c->xt);
+    }
+    transform_pass(c, T, 0, true, c->xt, x);
+    double res = 0.0;
+    if (sine) {
+        // || b - A x || with the boundary still frozen, then CG's end BC
+        ST_TRY(residual(&res));
+        if (neumann) launch_bc(c, x, 0, dv);  // linear_solver_cg.c:447
+    } else {
+        launch_bc(c, x, 0, dv);  // the iterations' apply_bc
+        ST_TRY(residual(&res));
+    }
+    HIP_TRY(hipEventRecord(c->tr_ev[1], c->stream));
+    HIP_TRY(hipEventSynchronize(c->tr_ev[1]));
     flush_timing(c);
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->dst_ev[0], c->dst_ev[1]));
-    const double res = s1.res0;
-    const bool conv = (res < s0.tol) || (res < abs_tol);
+    HIP_TRY(hipEventElapsedTime(&ms, c->tr_ev[0], c->tr_ev[1]));
+    const bool conv = (res < tol) || (res < abs_tol);
     c->pstats.status = conv ? POISSON_CONVERGED : POISSON_MAX_ITER;
     c->pstats.iterations = 1;
     c->pstats.final_residual = res;

@@ -1,8 +1,8 @@
 /*
- * dst_tables.h -- the host tables of the direct sine-transform pressure solver
- * (hip/dst_solve.hpp): the type-I sine matrix S_n and the eigenvalues of the
- * 1-D second difference with zero Dirichlet ends, for n interior points; and,
- * further down, the cosine tables of hip/dct_solve.hpp.
+ * dst_tables.h -- the host tables of the direct transform pressure solvers
+ * (hip/transform_solve.hpp). Sine: the type-I sine matrix S_n and the
+ * eigenvalues of the 1-D second difference with zero Dirichlet ends, for n
+ * interior points; further down, the cosine tables.
  * Shared by the device library and by host-only drivers that run the builders
  * under AddressSanitizer (tests/test_dst_cases.py, tests/test_dct_cases.py).
  *
@@ -64,7 +64,7 @@ static inline void dst_fill_eigenvalues(size_t n, double* eig) {
 }
 
 /*
- * The tables of the direct cosine-transform solve (hip/dct_solve.hpp): the
+ * The tables of the direct cosine-transform solve (hip/transform_solve.hpp): the
  * orthonormal type-II cosine matrix Q_n and the eigenvalues of the 1-D second
  * difference with Neumann (mirror) ends on n cell centres.
  *

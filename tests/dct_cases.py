@@ -1,5 +1,5 @@
 """Shapes, inputs and the numpy float64 model of the direct cosine-transform
-pressure solve (HIP_POISSON_DCT, cfd_amd/csrc/hip/dct_solve.hpp), shared by
+pressure solve (HIP_POISSON_DCT, cfd_amd/csrc/hip/transform_solve.hpp), shared by
 tests/test_dct_cases.py (the model against the oracle's RB-SOR and Jacobi, on
 the CPU) and tests/test_gpu_dct.py (the device against both).
 

@@ -1,5 +1,5 @@
 """Shapes, inputs and the numpy float64 model of the direct sine-transform
-pressure solve (HIP_POISSON_DST, cfd_amd/csrc/hip/dst_solve.hpp), shared by
+pressure solve (HIP_POISSON_DST, cfd_amd/csrc/hip/transform_solve.hpp), shared by
 tests/test_dst_cases.py (the model against the oracle's CG, on the CPU) and
 tests/test_gpu_dst.py (the device against both).
 

@@ -1,5 +1,5 @@
 """The direct cosine-transform pressure solve on the CPU: the numpy float64
-model of tests/dct_cases.py (the algorithm of cfd_amd/csrc/hip/dct_solve.hpp)
+model of tests/dct_cases.py (the algorithm of cfd_amd/csrc/hip/transform_solve.hpp)
 against the oracle's RB-SOR and Jacobi run to 1e-15 on every shape of the
 table; the incompatible right-hand side; the model's stats rules; planted
 bugs; the public surface; the host table builder under ASan + UBSan; and the

@@ -1,5 +1,5 @@
 """The direct sine-transform pressure solve on the CPU: the numpy float64 model
-of tests/dst_cases.py (the algorithm of cfd_amd/csrc/hip/dst_solve.hpp) against
+of tests/dst_cases.py (the algorithm of cfd_amd/csrc/hip/transform_solve.hpp) against
 the oracle's CG run to 1e-13, on every shape of the table, with the default
 Neumann apply_bc and with a Dirichlet hook; the model's stats rules; planted
 bugs; the public surface; the host table builder under ASan + UBSan.

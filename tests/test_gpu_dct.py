@@ -1,5 +1,5 @@
 """The direct cosine-transform pressure solve on the device (HIP_POISSON_DCT,
-dct_solve.hpp: the passes k_dst_x and k_dst_strided with cosine tables, the
+transform_solve.hpp: the passes k_dst_x and k_dst_strided with cosine tables, the
 negating load and the cosine eigenvalue division) on the shape table of
 tests/dct_cases.py.
 

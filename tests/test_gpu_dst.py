@@ -1,5 +1,5 @@
 """The direct sine-transform pressure solve on the device (HIP_POISSON_DST,
-dst_solve.hpp: k_dst_x and k_dst_strided on the fp64 matrix cores) on the shape
+transform_solve.hpp: k_dst_x and k_dst_strided on the fp64 matrix cores) on the shape
 table of tests/dst_cases.py.
 
 - each transform pass alone (hip_proj_dst_transform) against the long-double
