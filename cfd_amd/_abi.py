@@ -154,6 +154,17 @@ class DerivedFields(C.Structure):
                 ("vel_mag_stats", FieldStats), ("stats_computed", C.c_int)]
 
 
+# cfd_flow_diag_t and the `what` bits (include/cfd_hip/flow_diagnostics.h)
+HIP_DIAG_DIVERGENCE = 1
+HIP_DIAG_ENERGY = 2
+
+
+class FlowDiag(C.Structure):
+    _fields_ = [("div_linf", C.c_double), ("div_sumsq", C.c_double), ("div_l2", C.c_double),
+                ("div_cells", C.c_ulonglong), ("div_nan_cells", C.c_ulonglong),
+                ("ke", C.c_double), ("ke_rho", C.c_double), ("ke_rho_cells", C.c_double)]
+
+
 PROFILE_HORIZONTAL = 0
 PROFILE_VERTICAL = 1
 

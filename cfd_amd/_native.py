@@ -154,6 +154,8 @@ def _bind_host(lib) -> None:
          A.c_double_p, A.c_double_p, C.c_size_t, C.c_size_t, C.c_int)
     _sig(lib, "write_csv_statistics", None, C.c_char_p, C.c_int, C.c_double, P(A.FlowField),
          P(A.DerivedFields), C.c_size_t, C.c_size_t, C.c_int)
+    _sig(lib, "cfd_flow_diagnostics", C.c_int, P(A.FlowField), P(A.Grid), C.c_double, C.c_int,
+         P(A.FlowDiag))
     _sig(lib, "poisson_solver_params_default", A.PoissonParams)
     _sig(lib, "poisson_solver_stats_default", A.PoissonStats)
     _sig(lib, "poisson_solver_backend_available", C.c_bool, C.c_int)
@@ -253,6 +255,8 @@ def _bind_hip(lib) -> None:
     _sig(lib, "hip_proj_field_statistics", C.c_int, V, C.c_int, P(A.FieldStats))
     _sig(lib, "hip_proj_derived_statistics", C.c_int, V, C.c_int, C.c_double, P(A.DerivedFields))
     _sig(lib, "hip_proj_velocity_magnitude", C.c_int, V, A.c_double_p)
+    _sig(lib, "hip_proj_flow_diagnostics", C.c_int, V, P(A.Grid), C.c_double, C.c_int,
+         P(A.FlowDiag))
     _sig(lib, "hip_proj_write_csv_timeseries", C.c_int, V, C.c_char_p, C.c_int, C.c_double,
          P(A.SolverParams), P(A.SolverStats), C.c_int, C.c_int)
     _sig(lib, "hip_proj_write_csv_statistics", C.c_int, V, C.c_char_p, C.c_int, C.c_double,

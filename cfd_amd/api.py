@@ -248,6 +248,17 @@ def calculate_field_statistics(data: np.ndarray) -> A.FieldStats:
     return _native.host().calculate_field_statistics(a.ctypes.data_as(A.c_double_p), a.size)
 
 
+def flow_diagnostics(field: FlowField, grid: Grid, rho0: float = 1.0,
+                     what: int = 3) -> A.FlowDiag:
+    """cfd_flow_diagnostics (libcfd_host.so): the divergence norms and kinetic
+    energies of host arrays with the reference's sequential loops
+    (flow_diagnostics.h); field.rho is the density."""
+    d = A.FlowDiag()
+    _check(_native.host().cfd_flow_diagnostics(field.ptr, grid.ptr, rho0, what, C.byref(d)),
+           "cfd_flow_diagnostics")
+    return d
+
+
 class DerivedFields:
     """derived_fields_create / _compute_velocity_magnitude / _compute_statistics /
     _clear / _destroy of the host mirror (derived_fields.c:27-224)."""
@@ -680,6 +691,17 @@ class HipProjection:
         d.nx, d.ny, d.nz = self.shape[2], self.shape[1], self.shape[0]
         _check(self._lib().hip_proj_derived_statistics(self._ctx, int(with_vel_mag), rho0,
                                                        C.byref(d)), "hip_proj_derived_statistics")
+        return d
+
+    def flow_diagnostics(self, g: Grid, rho0: float = 1.0, what: int = 3) -> A.FlowDiag:
+        """hip_proj_flow_diagnostics: the divergence norms (what & 1) and the
+        kinetic energies (what & 2) of the resident u, v, w in one launch;
+        rho is the resident HIP_FIELD_RHO where the context holds it, else
+        rho0. div_linf skips NaN cells (the reference's loop): read
+        div_nan_cells beside it."""
+        d = A.FlowDiag()
+        _check(self._lib().hip_proj_flow_diagnostics(self._ctx, g.ptr, rho0, what, C.byref(d)),
+               "hip_proj_flow_diagnostics")
         return d
 
     def velocity_magnitude(self) -> np.ndarray:

@@ -160,6 +160,9 @@ struct hip_proj_ctx : TilePlan {
     // magnitude in the padded layout
     double* dstat = nullptr;
     double* vmag = nullptr;
+    // flow diagnostics (flow_diag.hip), allocated by the first such call: the
+    // workgroup records, the totals and the ticket of its one launch
+    double* fdiag = nullptr;
     double* partials = nullptr;
     unsigned* counter = nullptr;
     unsigned long long* red = nullptr;   // [0] max |u|^2, [1] max |p|, [2] nonfinite, [3] max T, [4] residual

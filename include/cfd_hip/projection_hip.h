@@ -430,6 +430,10 @@ CFD_HIP_EXPORT cfd_status_t hip_proj_write_csv_centerline(hip_proj_ctx_t* ctx,
                                                           profile_direction direction,
                                                           double rho0, int with_vel_mag);
 
+/* ---- flow diagnostics of the resident state: divergence norms and kinetic
+ * energy in one launch (hip_proj_flow_diagnostics, cfd_flow_diag_t) ---- */
+#include "cfd_hip/flow_diagnostics.h"
+
 /* Standalone pressure-Poisson solve on host buffers, the HIP counterpart of
  * poisson_solver_solve with a POISSON_BACKEND_GPU solver (linear_solver.c:487-509,
  * poisson_solver_cg_gpu.cu:135-178): upload x and rhs, solve lap(x) = rhs with
