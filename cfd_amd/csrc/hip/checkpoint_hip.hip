@@ -21,6 +21,12 @@
 // A read lands in scratch fields first and replaces the state only when the
 // trailing CRC matches, so a corrupt file leaves the context untouched; the
 // borrowed scratch is zeroed again afterwards.
+//
+// CFD_HIP_CHK_STAGE_BYTES=N caps one staging buffer at N bytes instead of
+// 64 MiB (unset or N <= 0: 64 MiB; never below one plane). A buffer holds
+// max(1, min(nz, N / (nx ny 8))) planes, so a small N runs the many-chunk
+// pipeline of a 512^3 state (short tail chunk, buffer reuse) on a small grid.
+// It is read on every write / read call.
 #include "ctx.hpp"
 
 #include "../host/chk_format.h"
@@ -135,10 +141,17 @@ void scrub_scratch(hip_proj_ctx* c, double* a, double* b) {
     hipStreamSynchronize(c->stream);
 }
 
-// staging: whole planes, about 64 MB per buffer
+// staging: whole planes, about 64 MB per buffer (CFD_HIP_CHK_STAGE_BYTES, read
+// on every write / read call: a context's planning knobs are fixed at its
+// creation, this one belongs to the call)
 size_t stage_planes(const hip_proj_ctx* c) {
+    size_t cap = 64u << 20;
+    if (const char* e = getenv("CFD_HIP_CHK_STAGE_BYTES")) {
+        const long long v = atoll(e);
+        if (v > 0) cap = (size_t)v;
+    }
     const size_t plane = c->nx * c->ny * sizeof(double);
-    return std::max<size_t>(1, std::min<size_t>(c->nz, (64u << 20) / std::max<size_t>(plane, 1)));
+    return std::max<size_t>(1, std::min<size_t>(c->nz, cap / std::max<size_t>(plane, 1)));
 }
 
 cfd_status_t crc_tables(hip_proj_ctx* c, DevCrcTab** out) {
@@ -218,14 +231,16 @@ cfd_status_t hip_proj_checkpoint_write(hip_proj_ctx_t* c, const char* path, cons
         set_err(CFD_ERROR_INVALID, "hip_proj_checkpoint_write: NULL argument");
         return CFD_ERROR_INVALID;
     }
-    if (g->nx != c->nx || g->ny != c->ny || g->nz != c->nz) {
-        set_err(CFD_ERROR_INVALID, "hip_proj_checkpoint_write: grid/context dimension mismatch");
-        return CFD_ERROR_INVALID;
-    }
+    // before the dimensions: a slab's nz is its local one, so the global grid
+    // would otherwise read as a mismatch
     if (dist(c) || !chk_host_little_endian()) {
         set_err(CFD_ERROR_UNSUPPORTED,
                 "hip_proj_checkpoint_write: Z-slab contexts / big-endian hosts not supported");
         return CFD_ERROR_UNSUPPORTED;
+    }
+    if (g->nx != c->nx || g->ny != c->ny || g->nz != c->nz) {
+        set_err(CFD_ERROR_INVALID, "hip_proj_checkpoint_write: grid/context dimension mismatch");
+        return CFD_ERROR_INVALID;
     }
     HIP_TRY(hipSetDevice(c->device));
     // u, v, w, p, rho, T: a context without a per-cell density or temperature
